@@ -10,9 +10,16 @@ xGMI) inside the timed region.
 
 `python bench.py --gpus N` with WORLD_SIZE unset starts the N rank processes itself
 (torch.distributed.run, before anything touches the GPU) and exits with their status;
-a rank whose world differs from --gpus exits non-zero.  Before timing, rank 0 inflates the
-stitched N-rank stream (header + chunks + combined Adler-32) and compares it with every
-rank's input: a wrong stream makes the run fail.
+a rank whose world differs from --gpus exits non-zero.
+
+A plain run sets up, runs --warmup steps, times --steps steps (no event inside the timed
+region), writes the last step's outputs if --dump-outputs DIR is given, and prints the line:
+value, ms_per_step, ratio and the configuration.  --full adds everything else, as separate
+passes outside the timed region: before timing, the stream is inflated (zlib, and on the GPU)
+and compared with the input -- N > 1: rank 0 inflates the stitched N-rank stream (header +
+chunks + combined Adler-32) against every rank's input -- and a wrong stream makes the run
+fail; then the per-stage and roofline figures, the long run, the tradeoff / exhaustive /
+real-text / fd API legs and the CPU baselines with their parity checks.
 
 Prints ONE JSON line on rank 0 (see DESIGN.md §5 for the roofline accounting).
 """
@@ -97,6 +104,14 @@ def parse_args(argv=None):
                          "default: the committed tools/roofline_counters.json")
     ap.add_argument("--launch-check", action="store_true",
                     help="test hook: start the ranks and check the world over gloo, no GPU work")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the stream checks (zlib and GPU "
+                         "inflate, the stitched N-rank stream), per-stage and roofline figures, the long run, "
+                         "the tradeoff / exhaustive / real-text / fd API legs and the CPU baselines (the options "
+                         "above that size those legs apply only with --full)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (this rank's stream "
+                         "and its result record) as DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -414,6 +429,46 @@ def roofline_counters(kname: str, parse: str, workload: str):
     return {**k, "source": c.get("source")}, None
 
 
+DUMP_SAMPLE = 1 << 23   # stream bytes kept by --dump-outputs (float32: 32 MiB)
+DUMP_CHUNK = 4096       # ... and the chunk of the checksums over the whole stream
+
+
+def dump_outputs(path: str, suffix: str, stream_bytes, res) -> dict:
+    """--dump-outputs: what a caller of the timed path receives from its last step, as .npy:
+      result        -- the result record (out_len, end_bits, n, ntokens, adler, status, block counts), float64;
+      stream        -- the stream's bytes as float32: all of them up to DUMP_SAMPLE bytes, else the bytes at
+                       DUMP_SAMPLE sorted positions drawn with a fixed seed from [0, out_len);
+      stream_sums   -- per DUMP_CHUNK-byte chunk of the whole stream, the sum of its bytes and the sum of
+                       (offset in chunk + 1) * byte, float64 (exact): a larger stream than the sample covers
+                       is still compared everywhere."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    s = np.asarray(stream_bytes, dtype=np.uint8)
+    fields = ("out_len", "end_bits", "n", "ntokens", "adler", "status", "nblocks", "nstored", "nfixed", "ndynamic",
+              "nsortfallback")
+    out = {"result": np.array([float(getattr(res, k)) for k in fields], dtype=np.float64)}
+    if s.size > DUMP_SAMPLE:
+        pos = np.sort(np.random.default_rng(0xD0F1A7E).integers(0, s.size, DUMP_SAMPLE))
+        out["stream"] = s[pos].astype(np.float32)
+    else:
+        out["stream"] = s.astype(np.float32)
+    nchunk = -(-s.size // DUMP_CHUNK)
+    pad = np.zeros(nchunk * DUMP_CHUNK, dtype=np.uint8)
+    pad[:s.size] = s
+    pad = pad.reshape(nchunk, DUMP_CHUNK)
+    w = np.arange(1, DUMP_CHUNK + 1, dtype=np.float64)
+    sums = np.empty((nchunk, 2), dtype=np.float64)
+    for lo in range(0, nchunk, 1024):   # 4 MiB of the stream at a time
+        c = pad[lo:lo + 1024].astype(np.float64)
+        sums[lo:lo + 1024, 0] = c.sum(axis=1)
+        sums[lo:lo + 1024, 1] = c @ w
+    out["stream_sums"] = sums
+    for k, v in out.items():
+        np.save(os.path.join(path, f"{k}{suffix}.npy"), v)
+    return {"dir": path, "arrays": {f"{k}{suffix}": list(v.shape) for k, v in out.items()}, "result_fields": fields,
+            "stream_sampled": bool(s.size > DUMP_SAMPLE)}
+
+
 def main() -> int:
     # The contract is ONE JSON line on stdout.  Libraries print there too (RCCL's version
     # banner at communicator creation), so fd 1 points at stderr for the whole run and the
@@ -425,6 +480,9 @@ def main() -> int:
     os.environ.setdefault("OMP_WAIT_POLICY", "PASSIVE")
     if args.gpus < 1:
         log("bench: --gpus must be >= 1")
+        return 2
+    if args.steps < 1 or args.warmup < 0:
+        log("bench: --steps must be >= 1 and --warmup >= 0")
         return 2
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return spawn_ranks(args, argv)   # before any GPU call in this process
@@ -551,124 +609,127 @@ def main() -> int:
             for _ in range(steps):
                 step()
 
-    # correctness of the measured configuration (outside the timed region)
-    run(1)
-    torch.cuda.synchronize(dev)
-    res = enc.result(stream)
-    out_len = int(res.out_len)
     ok = True
     stitched = None
     z = None
-    if world == 1:
-        z = d_out[:out_len].cpu().numpy().tobytes()
-        ok = zlib.decompress(z) == host.tobytes()
-        if not ok:
-            log("ERROR: stream does not inflate to the input")
-    else:
-        # rank 0 stitches every rank's chunk (header on rank 0's, sync flushes between, BFINAL
-        # on the last) with the combined Adler-32 and inflates it against every rank's input
-        comm_s = torch.cuda.current_stream(dev)
-        torch.cuda.synchronize(dev)
-        outs, glens = S.gather_chunks(last_buf[0], out_len, root=0)
-        meta = torch.tensor([n, int(res.adler)], dtype=torch.int64, device=dev)
-        metas = [torch.zeros(2, dtype=torch.int64, device=dev) for _ in range(world)]
-        dist.all_gather(metas, meta)
-        comm_s.synchronize()
-        flag = torch.zeros(1, dtype=torch.int64, device=dev)
-        if rank == 0:
-            ns = [int(m[0].item()) for m in metas]
-            ads = [int(m[1].item()) for m in metas]
-            chunks = [o.cpu().numpy().tobytes() for o in outs]
-            if strong:
-                bounds = [S.shard_range(per_rank, r, world) for r in range(world)]
-                pieces = [(lambda lo=lo, hi=hi: full[lo:hi].tobytes()) for lo, hi in bounds]
-            else:
-                pieces = [(lambda r=r: make_input(gen, per_rank, seed + r).tobytes()) for r in range(world)]
-            t0 = time.perf_counter()
-            ok = verify_stitched(chunks, ads, ns, pieces)
-            stitched = {"inflates": ok, "bytes": sum(len(c) for c in chunks) + 4, "input_bytes": sum(ns),
-                        "check_s": round(time.perf_counter() - t0, 2),
-                        "how": "rank 0: chunks gathered over RCCL + combined Adler-32 trailer, zlib inflate, "
-                               "compared with every rank's input"}
-            if not ok:
-                log("ERROR: the stitched multi-rank stream does not inflate to the ranks' inputs")
-            flag[0] = 1 if ok else 0
-        dist.broadcast(flag, 0)
-        ok = bool(flag.item())
-        del full
-    # GPU inflate of the same stream: every block decoded in parallel from the
-    # encoder's block index, compared bit for bit with the input; timed with events.  Dict
-    # streams reference the previous block: the chained decode (cells + pointer jumping,
-    # dmx_inflate_chained_async), also every block in parallel.
-    ix, nblk = enc.block_index()
-    dec = torch.empty(n, dtype=torch.uint8, device=dev)
-    ist = torch.zeros(16, dtype=torch.uint8, device=dev)
-    Lib = D.lib()
-    inf_src = last_buf[0]
-    chained = bool(args.dict)
-    work = None
-    if chained:
-        wb = int(Lib.dmx_inflate_chained_work(n, nblk))
-        work = torch.empty(wb + 256, dtype=torch.uint8, device=dev)
-        wptr = (work.data_ptr() + 255) & ~255
-
-    def inflate():
-        if chained:
-            rc = Lib.dmx_inflate_chained_async(inf_src.data_ptr(), out_len, ix.data_ptr(), nblk, dec.data_ptr(), n,
-                                               wptr, wb, ist.data_ptr(), stream)
-        else:
-            rc = Lib.dmx_inflate_async(inf_src.data_ptr(), out_len, ix.data_ptr(), nblk, dec.data_ptr(), n,
-                                       ist.data_ptr(), stream)
-        if rc != 0:
-            raise RuntimeError(f"GPU inflate launch: {rc}")
-
-    if world == 1 or not chained:
-        inflate()
-    torch.cuda.synchronize(dev)
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ev0.record()
-    inf_reps = 3 if (world == 1 or not chained) else 0
-    for _ in range(inf_reps):
-        inflate()
-    ev1.record()
-    torch.cuda.synchronize(dev)
     gpu_inflate = None
-    if inf_reps:
-        inf_ms = ev0.elapsed_time(ev1) / inf_reps
-        h = ist.cpu().numpy()
-        inf_status = int(np.frombuffer(h[:4].tobytes(), np.int32)[0])
-        inf_len = int(np.frombuffer(h[8:16].tobytes(), np.uint64)[0])
-        inf_ok = inf_status == 0 and inf_len == n and bool(torch.equal(dec, d_in))
-        if not inf_ok:
-            log(f"ERROR: GPU inflate status {inf_status}, {inf_len} of {n} bytes, or a byte mismatch")
-            ok = False
-        gpu_inflate = {"GBps_out": round(n / inf_ms / 1e6, 3), "ms": round(inf_ms, 4), "bit_exact": inf_ok,
-                       "mode": "chained: every block in parallel into 16-bit cells (references to the bytes "
-                               "before the block), references resolved by pointer jumping" if chained else
-                               "indexed: one single-wave workgroup per block",
-                       "kernel": "dmx_inflate_index_kernel<true> + dmx_cells_*" if chained else
-                                 "dmx_inflate_index_kernel"}
-        if chained:   # how fast the chains resolve: reference-list lengths after prep and each jump launch
-            lists = (ctypes.c_uint32 * 41)()
-            if Lib.dmx_inflate_chained_lists(wptr, lists, 41, stream) == 0:
-                ls = list(lists)
-                while len(ls) > 1 and ls[-1] == 0 and ls[-2] == 0:
-                    ls.pop()
-                gpu_inflate["reference_lists"] = ls
-    del work
-    del dec
+    if args.full:
+        # correctness of the measured configuration (outside the timed region)
+        run(1)
+        torch.cuda.synchronize(dev)
+        res = enc.result(stream)
+        out_len = int(res.out_len)
+        if world == 1:
+            z = d_out[:out_len].cpu().numpy().tobytes()
+            ok = zlib.decompress(z) == host.tobytes()
+            if not ok:
+                log("ERROR: stream does not inflate to the input")
+        else:
+            # rank 0 stitches every rank's chunk (header on rank 0's, sync flushes between, BFINAL
+            # on the last) with the combined Adler-32 and inflates it against every rank's input
+            comm_s = torch.cuda.current_stream(dev)
+            torch.cuda.synchronize(dev)
+            outs, glens = S.gather_chunks(last_buf[0], out_len, root=0)
+            meta = torch.tensor([n, int(res.adler)], dtype=torch.int64, device=dev)
+            metas = [torch.zeros(2, dtype=torch.int64, device=dev) for _ in range(world)]
+            dist.all_gather(metas, meta)
+            comm_s.synchronize()
+            flag = torch.zeros(1, dtype=torch.int64, device=dev)
+            if rank == 0:
+                ns = [int(m[0].item()) for m in metas]
+                ads = [int(m[1].item()) for m in metas]
+                chunks = [o.cpu().numpy().tobytes() for o in outs]
+                if strong:
+                    bounds = [S.shard_range(per_rank, r, world) for r in range(world)]
+                    pieces = [(lambda lo=lo, hi=hi: full[lo:hi].tobytes()) for lo, hi in bounds]
+                else:
+                    pieces = [(lambda r=r: make_input(gen, per_rank, seed + r).tobytes()) for r in range(world)]
+                t0 = time.perf_counter()
+                ok = verify_stitched(chunks, ads, ns, pieces)
+                stitched = {"inflates": ok, "bytes": sum(len(c) for c in chunks) + 4, "input_bytes": sum(ns),
+                            "check_s": round(time.perf_counter() - t0, 2),
+                            "how": "rank 0: chunks gathered over RCCL + combined Adler-32 trailer, zlib inflate, "
+                                   "compared with every rank's input"}
+                if not ok:
+                    log("ERROR: the stitched multi-rank stream does not inflate to the ranks' inputs")
+                flag[0] = 1 if ok else 0
+            dist.broadcast(flag, 0)
+            ok = bool(flag.item())
+            del full
+        # GPU inflate of the same stream: every block decoded in parallel from the
+        # encoder's block index, compared bit for bit with the input; timed with events.  Dict
+        # streams reference the previous block: the chained decode (cells + pointer jumping,
+        # dmx_inflate_chained_async), also every block in parallel.
+        ix, nblk = enc.block_index()
+        dec = torch.empty(n, dtype=torch.uint8, device=dev)
+        ist = torch.zeros(16, dtype=torch.uint8, device=dev)
+        Lib = D.lib()
+        inf_src = last_buf[0]
+        chained = bool(args.dict)
+        work = None
+        if chained:
+            wb = int(Lib.dmx_inflate_chained_work(n, nblk))
+            work = torch.empty(wb + 256, dtype=torch.uint8, device=dev)
+            wptr = (work.data_ptr() + 255) & ~255
+
+        def inflate():
+            if chained:
+                rc = Lib.dmx_inflate_chained_async(inf_src.data_ptr(), out_len, ix.data_ptr(), nblk, dec.data_ptr(), n,
+                                                   wptr, wb, ist.data_ptr(), stream)
+            else:
+                rc = Lib.dmx_inflate_async(inf_src.data_ptr(), out_len, ix.data_ptr(), nblk, dec.data_ptr(), n,
+                                           ist.data_ptr(), stream)
+            if rc != 0:
+                raise RuntimeError(f"GPU inflate launch: {rc}")
+
+        if world == 1 or not chained:
+            inflate()
+        torch.cuda.synchronize(dev)
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        inf_reps = 3 if (world == 1 or not chained) else 0
+        for _ in range(inf_reps):
+            inflate()
+        ev1.record()
+        torch.cuda.synchronize(dev)
+        if inf_reps:
+            inf_ms = ev0.elapsed_time(ev1) / inf_reps
+            h = ist.cpu().numpy()
+            inf_status = int(np.frombuffer(h[:4].tobytes(), np.int32)[0])
+            inf_len = int(np.frombuffer(h[8:16].tobytes(), np.uint64)[0])
+            inf_ok = inf_status == 0 and inf_len == n and bool(torch.equal(dec, d_in))
+            if not inf_ok:
+                log(f"ERROR: GPU inflate status {inf_status}, {inf_len} of {n} bytes, or a byte mismatch")
+                ok = False
+            gpu_inflate = {"GBps_out": round(n / inf_ms / 1e6, 3), "ms": round(inf_ms, 4), "bit_exact": inf_ok,
+                           "mode": "chained: every block in parallel into 16-bit cells (references to the bytes "
+                                   "before the block), references resolved by pointer jumping" if chained else
+                                   "indexed: one single-wave workgroup per block",
+                           "kernel": "dmx_inflate_index_kernel<true> + dmx_cells_*" if chained else
+                                     "dmx_inflate_index_kernel"}
+            if chained:   # how fast the chains resolve: reference-list lengths after prep and each jump launch
+                lists = (ctypes.c_uint32 * 41)()
+                if Lib.dmx_inflate_chained_lists(wptr, lists, 41, stream) == 0:
+                    ls = list(lists)
+                    while len(ls) > 1 and ls[-1] == 0 and ls[-2] == 0:
+                        ls.pop()
+                    gpu_inflate["reference_lists"] = ls
+        del work
+        del dec
     run(args.warmup)
     torch.cuda.synchronize(dev)
-    # every stage's HIP-event time from an untimed pass (an event at every stage boundary costs
-    # a few us of idle per boundary: on C4 that was 0.48 -> 0.59 ms per step); the timed region
-    # then records only the dominant stage's two events, for the roofline's launch time, on
-    # every TIMING_EVERY-th step (a sample of the timed steps, at a quarter of the idle)
-    enc.set_timing(True)
-    run(max(args.steps, 1))
-    torch.cuda.synchronize(dev)
-    stage_ms, nstage = enc.stage_times()
-    dom = max((k for k in stage_ms if k != "total"), key=stage_ms.get)
-    enc.set_timing(True, stage=dom, every=TIMING_EVERY)
+    if args.full:
+        # every stage's HIP-event time from an untimed pass (an event at every stage boundary costs
+        # a few us of idle per boundary: on C4 that was 0.48 -> 0.59 ms per step); the timed region
+        # then records only the dominant stage's two events, for the roofline's launch time, on
+        # every TIMING_EVERY-th step (a sample of the timed steps, at a quarter of the idle).
+        # A plain run records no event at all.
+        enc.set_timing(True)
+        run(max(args.steps, 1))
+        torch.cuda.synchronize(dev)
+        stage_ms, nstage = enc.stage_times()
+        dom = max((k for k in stage_ms if k != "total"), key=stage_ms.get)
+        enc.set_timing(True, stage=dom, every=TIMING_EVERY)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize(dev)
@@ -678,15 +739,22 @@ def main() -> int:
     if world > 1:
         dist.barrier()
     t1 = time.perf_counter()
-    dom_ms_timed, dom_n_timed = enc.stage_times()
-    dom_ms_timed = dom_ms_timed[dom]
-    enc.set_timing(False)
+    if args.full:
+        dom_ms_timed, dom_n_timed = enc.stage_times()
+        dom_ms_timed = dom_ms_timed[dom]
+        enc.set_timing(False)
     dt = t1 - t0
-    fb_total = int(enc.result(stream).nsortfallback_total)   # every encode of this context so far
+    res = enc.result(stream)   # the last timed step's
+    out_len = int(res.out_len)
+    fb_total = int(res.nsortfallback_total)   # every encode of this context so far
+    dumped = None
+    if args.dump_outputs:   # before any further leg encodes into the same buffer
+        dumped = dump_outputs(args.dump_outputs, f"_rank{rank}" if world > 1 else "",
+                              last_buf[0][:out_len].cpu().numpy(), res)
     # a longer run of the same step (outside the timed region): the timed region above is what
     # the driver asked for; this shows the rate holds over about a second of back-to-back steps
     long_run = None
-    if world == 1 and args.long_run > 0 and not pipelined:
+    if args.full and world == 1 and args.long_run > 0 and not pipelined:
         reps = max(args.steps, int(args.long_run / max(dt / max(args.steps, 1), 1e-4)))
         torch.cuda.synchronize(dev)
         q0 = time.perf_counter()
@@ -697,7 +765,7 @@ def main() -> int:
                     "ms_per_step": round((q1 - q0) / reps * 1e3, 4)}
     # the speed / size curve over max_chain, same input and flags (outside the timed region)
     tradeoff = []
-    if world == 1 and args.tradeoff and not pipelined:
+    if args.full and world == 1 and args.tradeoff and not pipelined:
         for kc in [int(x) for x in args.tradeoff.split(",") if x.strip()]:
             if kc == args.max_chain:
                 continue
@@ -715,7 +783,7 @@ def main() -> int:
                              "ratio": round(t_len / n, 5), "compressed_bytes": t_len, "steps": 5})
     exh = None
     exh_stream = None
-    if world == 1 and args.max_chain != 0 and args.exhaustive_steps > 0:
+    if args.full and world == 1 and args.max_chain != 0 and args.exhaustive_steps > 0:
         # the reference's own parse (every earlier position of the bucket), same input
         ex = D.Encoder(local, n, 32768, 0, flags & ~(D.DMX_F_LAZY | D.DMX_F_DICT | D.DMX_F_SPLIT | D.DMX_F_STORE_CHECK
                                                     | D.DMX_F_DEEP))
@@ -746,12 +814,42 @@ def main() -> int:
     if rank == 0:
         ms_step = dt / args.steps * 1e3
         value = tot_in * args.steps / dt / 1e9
+        parse = parse_str(args)
+        line = {
+            "metric": "encode GB/s (uncompressed in) + compression ratio vs CPU ref, 1/2/4/8 MI355X",
+            "value": round(value, 3),
+            "unit": "GB/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(ms_step, 4),
+            "higher_is_better": True,
+            "scaling": "strong" if strong else "weak",
+            "vs_baseline": None,
+            "dtype": "u8",
+            "data": "synthetic",
+            "config": {
+                "workload": desc,
+                "name": args.workload,
+                "bytes_per_rank": n,
+                "block": 32768,
+                "parse": parse,
+                "parallelism": f"blocks sharded over {world} GPU(s)" + (f", gather={args.gather}" if world > 1 else "")
+                               + (", pipelined" if pipelined else ""),
+            },
+            "full": bool(args.full),
+            "ratio": round(out_len / n, 5),
+            "nsortfallback": fb_total,
+            "compressed_bytes_rank0": out_len,
+            "compressed_bytes_all": tot_out,
+            "outputs": dumped,
+        }
+    if rank == 0 and args.full:
         kname = {"pre": "dmx_hist_kernel_t" if args.dict else "dmx_store_check_kernel",
                  "huff": "dmx_split_plan_kernel" if args.split else "dmx_huff_kernel"}.get(dom, f"dmx_{dom}_kernel")
         dom_ms = dom_ms_timed   # HIP events around the dominant stage inside the timed region
         algo_bytes = n + out_len   # per launch on this rank: input read + stream written
         achieved = algo_bytes / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
-        parse = parse_str(args)
         traffic, valu, why = None, None, None
         if args.traffic_csv:
             try:
@@ -821,38 +919,13 @@ def main() -> int:
                 if not parity_exh:
                     log("ERROR: GPU exhaustive stream differs from the CPU port's (the reference parse)")
                     ok = False
-        line = {
-            "metric": "encode GB/s (uncompressed in) + compression ratio vs CPU ref, 1/2/4/8 MI355X",
-            "value": round(value, 3),
-            "unit": "GB/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_step, 4),
-            "higher_is_better": True,
-            "scaling": "strong" if strong else "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": "synthetic",
-            "config": {
-                "workload": desc,
-                "name": args.workload,
-                "bytes_per_rank": n,
-                "block": 32768,
-                "parse": parse,
-                "parallelism": f"blocks sharded over {world} GPU(s)" + (f", gather={args.gather}" if world > 1 else "")
-                               + (", pipelined" if pipelined else ""),
-            },
-            "ratio": round(out_len / n, 5),
+        line.update({
             "parity_vs_port": parity,
-            "nsortfallback": fb_total,
             "size_vs_ref_pct": size_pct,
             "s_ref_bytes": s_ref_bytes,
             "exhaustive": exh,
             "tradeoff": tradeoff or None,
             "long_run": long_run,
-            "compressed_bytes_rank0": out_len,
-            "compressed_bytes_all": tot_out,
             "inflate_ok": ok,
             "stitched": stitched,
             "gpu_inflate": gpu_inflate,
@@ -888,9 +961,10 @@ def main() -> int:
             "real_text": real,
             "cpu_baseline_reference": cpu.get("reference"),
             "host": info,
-        }
+        })
         if base and base["value"]:
             line["gpu_over_cpu"] = round(value / base["value"], 1)
+    if rank == 0:
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(line) + "\n").encode())
     enc.close()

@@ -16,7 +16,7 @@ else
     timeout -k 10 120 python -c "
 import sys, runpy; sys.path.insert(0, '$R')
 import deflate_compression_amd as D; D.LIB_PATH = '$R/build/flagexp/libdmx_$n.so'
-sys.argv = ['bench.py', '--steps', '10', '--warmup', '3', '--cpu-budget', '0', '--tradeoff=', '--exhaustive-steps', '0']
+sys.argv = ['bench.py', '--full', '--steps', '10', '--warmup', '3', '--cpu-budget', '0', '--tradeoff=', '--exhaustive-steps', '0']
 runpy.run_path('$R/bench.py', run_name='__main__')" 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('$n', d['value'], d['ratio'], d['stage_ms'])" || exit 1
   done
 fi

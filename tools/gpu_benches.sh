@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 CFGS=${*:-random dict zeros split enwik9 trace}
-Q="--cpu-budget 0 --exhaustive-steps 0 --tradeoff= --long-run 0 --real-text 0"
+Q="--full --cpu-budget 0 --exhaustive-steps 0 --tradeoff= --long-run 0 --real-text 0"
 for c in $CFGS; do
     case $c in
         random) A="--workload random $Q" ;;

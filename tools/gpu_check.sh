@@ -19,7 +19,7 @@ timeout -k 10 900 python3 -u -m pytest "$R/tests" -m gpu -x -v -p no:cacheprovid
 rc=$?
 tail -4 "$OUT/pytest.log"
 if [ $rc -ne 0 ] && [ $rc -ne 1 ] && [ $rc -ne 5 ]; then echo "pytest status $rc: stopping"; exit $rc; fi
-timeout -k 10 600 python3 "$R/bench.py" "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 600 python3 "$R/bench.py" --full "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
 brc=$?
 tail -3 "$OUT/bench.err"
 python3 -c "

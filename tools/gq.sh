@@ -20,7 +20,7 @@ for st in "$@"; do
   name=${st%%:*}; arg=""; [ "$name" != "$st" ] && arg=${st#*:}
   case $name in
     bench) nb=$((nb + 1)); bj=$OUT/bench$([ $nb -gt 1 ] && echo $nb).json
-           timeout -k 10 600 python3 "$R/bench.py" ${arg//,/ } > "$bj" 2> "${bj%.json}.err" || exit 3
+           timeout -k 10 600 python3 "$R/bench.py" --full ${arg//,/ } > "$bj" 2> "${bj%.json}.err" || exit 3
            python3 - "$bj" <<'PY'
 import json, sys; d = json.load(open(sys.argv[1]))
 print('value', d['value'], 'size', d.get('size_vs_ref_pct'), 'parity', d.get('parity_vs_port'), 'stage', d['stage_ms'])
@@ -52,7 +52,7 @@ PY
     deep) lv=${arg#libv=}   # deep[:libv=NAME]
         ( [ -n "$arg" ] && export DMX_LIBV="$R/build/var/libdmx_$lv.so"; timeout -k 10 300 python3 "$R/tools/deep_bench.py" 32 ) >> "$OUT/deep.txt" 2>&1 || exit 3
         grep -v amdgpu "$OUT/deep.txt" | tail -4 ;;
-    trace) cd /tmp; timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- python3 "$R/bench.py" --steps 5 --warmup 1 --cpu-budget 0 --exhaustive-steps 0 --tradeoff= --long-run 0 ${arg//,/ } > "$OUT/bench_trace.json" 2> "$OUT/trace.err" || exit 3
+    trace) cd /tmp; timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- python3 "$R/bench.py" --full --steps 5 --warmup 1 --cpu-budget 0 --exhaustive-steps 0 --tradeoff= --long-run 0 ${arg//,/ } > "$OUT/bench_trace.json" 2> "$OUT/trace.err" || exit 3
            find "$OUT/trace" -name "*kernel_stats.csv" -exec cp {} "$OUT/kernel_stats.csv" \; ; cut -d, -f1-8 "$OUT/kernel_stats.csv" | head -20; cd "$R" ;;
     *) echo "unknown step $name"; exit 2 ;;
   esac

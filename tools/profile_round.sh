@@ -11,7 +11,7 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-BA="--cpu-budget 0 --exhaustive-steps 0 --tradeoff= --long-run 0 $*"
+BA="--full --cpu-budget 0 --exhaustive-steps 0 --tradeoff= --long-run 0 $*"
 echo "[1/6] pytest -m gpu"; timeout -k 10 900 python3 -u -m pytest "$R/tests" -m gpu -x -v -p no:cacheprovider --timeout 240 --timeout-method thread > "$OUT/pytest_gpu.log" 2>&1
 tail -2 "$OUT/pytest_gpu.log"
 echo "[2/6] kernel trace"; timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- python3 "$R/bench.py" --steps 5 --warmup 1 $BA > "$OUT/bench_trace.json" 2> "$OUT/trace.err"
@@ -33,5 +33,5 @@ cj = subprocess.check_output([sys.executable, f"{r}/tools/pmc.py", "--counters-j
 open(f"{out}/roofline_counters.json", "wb").write(cj)
 print(cj.decode())
 PY
-echo "[6/6] bench"; timeout -k 10 400 python3 "$R/bench.py" --traffic-csv "$OUT/pmc_f,$OUT/pmc_w" $* > "$OUT/bench.json" 2> "$OUT/bench.err"
+echo "[6/6] bench"; timeout -k 10 400 python3 "$R/bench.py" --full --traffic-csv "$OUT/pmc_f,$OUT/pmc_w" $* > "$OUT/bench.json" 2> "$OUT/bench.err"
 cat "$OUT/bench.json"
