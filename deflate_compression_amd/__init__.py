@@ -8,7 +8,7 @@ include/dmx.h).  This module is a thin ctypes layer:
         deflate_ext.h:17 / deflate_compress.c:362 -- 0 or -E_* (no exceptions, like C)
     deflate_decompress(data, ops=0) -> bytes
         deflate_ext.h:16 -- raises DeflateError(code) on a negative return
-    compress(data, sw=32768, max_chain=0) -> bytes        host buffer convenience
+    compress(data, sw=32768, max_chain=0) -> bytes        host buffer convenience (gzip=True: a .gz member)
     Encoder                                               device-resident encodes
 
 There is no CPU fallback: if libdmx.so is missing the import of this module fails,
@@ -23,7 +23,7 @@ import struct
 __all__ = [
     "DeflateError", "Opts", "Result", "Encoder", "lib", "compress", "deflate_compress",
     "deflate_decompress", "max_compressed", "adler32_combine", "gen_text", "gen_random",
-    "COMPRESS_STATS", "E", "DMX_F_HEADER", "DMX_F_TRAILER", "DMX_F_FINAL", "DMX_ZLIB", "DMX_F_LAZY", "DMX_F_EXACT_SORT", "DMX_F_SPLIT", "DMX_F_DICT", "DMX_F_STORE_CHECK", "DMX_F_DEEP", "inflate_gpu", "inflate_gpu_chained", "ref_estimates",
+    "COMPRESS_STATS", "E", "DMX_F_HEADER", "DMX_F_TRAILER", "DMX_F_FINAL", "DMX_ZLIB", "DMX_F_LAZY", "DMX_F_EXACT_SORT", "DMX_F_SPLIT", "DMX_F_DICT", "DMX_F_STORE_CHECK", "DMX_F_DEEP", "DMX_F_GZIP", "DMX_GZIP", "crc32_combine", "crc32_geometry", "inflate_gpu", "inflate_gpu_chained", "ref_estimates",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -39,6 +39,8 @@ DMX_F_SPLIT = 32
 DMX_F_DICT = 64
 DMX_F_STORE_CHECK = 128
 DMX_F_DEEP = 256
+DMX_F_GZIP = 512
+DMX_GZIP = DMX_ZLIB | DMX_F_GZIP
 _M = 1 << 24
 # src/include/global_errors.h:24-35 and src/include/deflate_errors.h:9-22
 E = {
@@ -116,6 +118,10 @@ def lib() -> ctypes.CDLL:
         "dmx_encode_fd_multi": ([ctypes.c_int, ctypes.c_int, ctypes.POINTER(Opts), u64,
                                  ctypes.POINTER(ctypes.c_int), ctypes.c_int], ctypes.c_int),
         "dmx_max_compressed": ([u64, i32], u64),
+        "dmx_max_compressed_flags": ([u64, i32, u32], u64),
+        "dmx_crc32_async": ([vp, vp, u64, vp, vp], ctypes.c_int),
+        "dmx_crc32_combine": ([u32, u32, u64], u32),
+        "dmx_crc32_geometry": ([u32p, u32p], None),
         "dmx_fd_last_stats": ([ctypes.POINTER(FdStats)], ctypes.c_int),
         "dmx_encode_async": ([vp, vp, u64, vp, u64, ctypes.POINTER(Opts), vp], ctypes.c_int),
         "dmx_encode_result": ([vp, ctypes.POINTER(Result), vp], ctypes.c_int),
@@ -178,21 +184,25 @@ def fd_last_stats() -> dict | None:
             for k, _ in FdStats._fields_}
 
 
-def max_compressed(n: int, sw: int = 32768) -> int:
-    return int(lib().dmx_max_compressed(n, sw))
+def max_compressed(n: int, sw: int = 32768, flags: int = DMX_ZLIB) -> int:
+    """Worst-case stream bytes for n input bytes (12 more for the gzip container, DMX_F_GZIP)."""
+    return int(lib().dmx_max_compressed_flags(n, sw, flags))
 
 
 def compress(data, sw: int = 32768, max_chain: int = 0, flags: int = DMX_ZLIB, lazy: bool = False,
              split: bool = False, dict: bool = False, pre=None, store_check: bool = False,
-             deep: bool = False) -> bytes:
-    """Encode a host buffer on the GPU; returns the zlib stream (or raw DEFLATE with flags).
+             deep: bool = False, gzip: bool = False) -> bytes:
+    """Encode a host buffer on the GPU; returns the zlib stream (or raw DEFLATE with flags;
+    gzip = a gzip member around the same DEFLATE data, DMX_F_GZIP).
     lazy = f2 lazy parse (DMX_F_LAZY), split = f3 adaptive block splitting (DMX_F_SPLIT),
     dict = f1 cross-block dictionary (DMX_F_DICT; pre = the bytes before `data`),
     store_check = noise blocks stored without a parse (DMX_F_STORE_CHECK),
     deep = adaptive chain depth of small-alphabet blocks (DMX_F_DEEP)."""
     L = lib()
     p, n, keep = _buf(data)
-    cap = max_compressed(n, sw)
+    if gzip:
+        flags |= DMX_F_GZIP
+    cap = max_compressed(n, sw, flags)
     out = ctypes.create_string_buffer(cap)
     olen = ctypes.c_uint64(0)
     o = Opts(sw, max_chain, flags | (DMX_F_LAZY if lazy else 0) | (DMX_F_SPLIT if split else 0) |
@@ -212,7 +222,7 @@ def deflate_compress(fd_in: int, fd_out: int, fd_stats: int = -1, sw: int = 3276
 
 
 def deflate_decompress(data, ops: int = 0) -> bytes:
-    """deflate_ext.h:16 -- inflate a zlib stream; raises DeflateError on -E_*."""
+    """deflate_ext.h:16 -- inflate a zlib stream or a gzip member; raises DeflateError on -E_*."""
     L = lib()
     b = bytes(data)
     src = (ctypes.c_ubyte * max(len(b), 1)).from_buffer_copy(b or b"\0")
@@ -306,6 +316,19 @@ def adler32_combine(a: int, b: int, len_b: int) -> int:
     return int(lib().dmx_adler32_combine(a, b, len_b))
 
 
+def crc32_combine(a: int, b: int, len_b: int) -> int:
+    """CRC-32 of A || B from crc(A), crc(B) and len(B) (dmx_crc32_combine; host only)."""
+    return int(lib().dmx_crc32_combine(a & 0xFFFFFFFF, b & 0xFFFFFFFF, len_b))
+
+
+def crc32_geometry() -> tuple[int, int]:
+    """(span, lane slice) in bytes of the CRC-32 kernel (dmx_crc32_geometry): a workgroup takes
+    a span, each of its lanes a contiguous slice of it."""
+    s, l = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    lib().dmx_crc32_geometry(ctypes.byref(s), ctypes.byref(l))
+    return int(s.value), int(l.value)
+
+
 def gen_text(n: int, seed: int = 0xE5818):
     import numpy as np
     a = np.empty(n, dtype=np.uint8)
@@ -376,6 +399,21 @@ class Encoder:
         memory, e.g. a pin_memory uint8 tensor); read it after the stream or an event."""
         _check(self._L.dmx_encode_result_async(self._ctx, ctypes.c_void_p(host_ptr), ctypes.c_void_p(stream or 0)),
                "dmx_encode_result_async")
+
+    def crc32(self, t, stream=None) -> int:
+        """CRC-32 (RFC 1952 / PNG) of a uint8 CUDA tensor, computed on the device
+        (dmx_crc32_async); the tensor's storage may start at any byte."""
+        import torch
+        n = t.numel()
+        self.reserve(n, 32768)
+        w = torch.empty(1, dtype=torch.int32, device=t.device)
+        s = stream if stream is not None else torch.cuda.current_stream(t.device).cuda_stream
+        if not s:   # the default stream's handle is NULL, which selects the context's own stream
+            torch.cuda.synchronize(t.device)
+        _check(self._L.dmx_crc32_async(self._ctx, ctypes.c_void_p(t.data_ptr() if n else 0), n,
+                                       ctypes.c_void_p(w.data_ptr()), ctypes.c_void_p(s)), "dmx_crc32_async")
+        torch.cuda.synchronize(t.device)
+        return int(w.item()) & 0xFFFFFFFF
 
     # -- introspection of the last encode (tests / stats) --
     def blocks(self, nblk: int):
@@ -489,7 +527,7 @@ class Encoder:
         o = opts or self.opts
         n = t_in.numel()
         self.reserve(n, o.sw, o.flags)
-        cap = max_compressed(n, o.sw)
+        cap = max_compressed(n, o.sw, o.flags)
         out = torch.empty(cap, dtype=torch.uint8, device=t_in.device)
         s = stream if stream is not None else torch.cuda.current_stream(t_in.device).cuda_stream
         self.encode_async(t_in.data_ptr() if n else out.data_ptr(), n, out.data_ptr(), cap, s, o)

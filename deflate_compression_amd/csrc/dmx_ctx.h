@@ -38,7 +38,10 @@ struct dmx_ctx {
     uint32_t* whint_dev;        // its device address (the scan kernel writes it when an encode runs without the lists)
     uint32_t ncu;     // compute units (the persistent K1 grid of the work-list mode)
     dmx_result* res;
-    uint32_t* nfb;        // [0] sort fallbacks of the encode in flight (kernels add, K3's scan reads and zeroes), [1] total
+    uint32_t* nfb;        // [0] sort fallbacks of the encode in flight (kernels add, K3's scan reads and zeroes), [1] total,
+                          // [2] the CRC-32 of a DMX_F_GZIP encode's input (dmx_crc.hip writes, K3's scan reads)
+    uint32_t* crc_rem;    // CRC-32 scratch (dmx_crc.hip): crc_cap span remainders
+    uint64_t crc_cap;     // spans of DMX_BLK bytes it holds: cap_blocks + 2 (0: no workspace yet)
     uint64_t* dbg;        // optional per-block phase stamps (DMX_STAMPS=1)
     uint64_t dbg_cap;
     // last encode (introspection)

@@ -57,7 +57,7 @@ extern "C" int dmx_encode_host(const uint8_t* in, uint64_t n, uint8_t* out, uint
     if (!r) {
         r = dmx_ctx_reserve_flags(c, n, o.sw, o.flags);
     }
-    const uint64_t dcap = dmx_max_compressed(n, o.sw);
+    const uint64_t dcap = dmx_max_compressed_flags(n, o.sw, o.flags);
     if (!r) r = ensure_buf(&c->d_in, &c->d_in_cap, n + 16);
     if (!r) r = ensure_buf(&c->d_out, &c->d_out_cap, dcap);
     if (!r && hip_fail(hipSetDevice(c->device), "hipSetDevice")) r = -(int)E_DEVICE;
@@ -541,6 +541,17 @@ extern "C" int dmx_encode_fd_cb(int fd_in, int fd_out, const dmx_opts* opts, uin
     return encode_fd_on(dev_s ? atoi(dev_s) : 0, fd_in, fd_out, opts, chunk, cb, user);
 }
 
+// the stream's trailer from the combined check value: Adler-32 big-endian, or (gzip) CRC-32
+// and the byte count mod 2^32, little-endian; returns its length
+static uint64_t stream_trailer(uint8_t* t, bool gz, uint32_t check, uint64_t total) {
+    if (!gz) {
+        for (int k = 0; k < 4; k++) t[k] = (uint8_t)(check >> (24 - 8 * k));
+        return 4;
+    }
+    for (int k = 0; k < 4; k++) { t[k] = (uint8_t)(check >> (8 * k)); t[4 + k] = (uint8_t)(total >> (8 * k)); }
+    return 8;
+}
+
 static int encode_fd_on(int device, int fd_in, int fd_out, const dmx_opts* opts, uint64_t chunk,
                         dmx_fd_chunk_cb cb, void* user) {
     dmx_opts o = {0, 0, DMX_ZLIB, 0, NULL, 0};
@@ -551,7 +562,8 @@ static int encode_fd_on(int device, int fd_in, int fd_out, const dmx_opts* opts,
     if (chunk < sw) chunk = sw;
     chunk -= chunk % sw;
     const uint32_t pflags = o.flags & (DMX_F_LAZY | DMX_F_SPLIT | DMX_F_DICT | DMX_F_EXACT_SORT | DMX_F_STORE_CHECK |
-                                       DMX_F_DEEP);
+                                       DMX_F_DEEP | DMX_F_GZIP);
+    const bool gz = (pflags & DMX_F_GZIP) != 0;   // one gzip member: CRC-32 where zlib has Adler-32
     FdReader R = {fd_in, false, 0, 0, -1, true};
     {   // a regular file of known size from the current offset: parallel preads
         struct stat st;
@@ -566,7 +578,7 @@ static int encode_fd_on(int device, int fd_in, int fd_out, const dmx_opts* opts,
     int err = 0;
     dmx_ctx* c = dmx_cached_ctx(device, chunk, &err);
     int r = err;
-    const uint64_t ocap = dmx_max_compressed(chunk, o.sw);
+    const uint64_t ocap = dmx_max_compressed_flags(chunk, o.sw, pflags);
     FdPipe* P = NULL;
     if (!r) r = dmx_ctx_reserve_flags(c, chunk, (int32_t)sw, pflags);
     if (!r && hip_fail(hipSetDevice(c->device), "hipSetDevice")) r = -(int)E_DEVICE;
@@ -587,7 +599,7 @@ static int encode_fd_on(int device, int fd_in, int fd_out, const dmx_opts* opts,
     if (!rstarted) fds_fail(&S, -(int)E_MALLOC);
     const bool wstarted = pthread_create(&wt, NULL, fdp_writer, &wj) == 0;
     if (!wstarted) fds_fail(&S, -(int)E_MALLOC);
-    uint32_t adler = 1;
+    uint32_t adler = gz ? 0u : 1u;   // the stream's check value so far
     uint64_t off = 0;   // offset of the chunk being finished in the bytes read (callback)
     uint64_t clen[2] = {0, 0};
     int cin[2] = {0, 0};   // the input slot of the chunk in device output k2 (its H2D events)
@@ -604,7 +616,8 @@ static int encode_fd_on(int device, int fd_in, int fd_out, const dmx_opts* opts,
         if (hipEventElapsedTime(&ems, P->te[k2], P->eve[k2]) == hipSuccess) enc_ms += ems;
         if (clen[k2] && hipEventElapsedTime(&hms, P->th[cin[k2]], P->evh[cin[k2]]) == hipSuccess) h2d_ms += hms;
         nout_total += olen;
-        adler = dmx_adler32_combine(adler, P->hres[k2]->adler, clen[k2]);
+        adler = gz ? dmx_crc32_combine(adler, P->hres[k2]->adler, clen[k2])
+                   : dmx_adler32_combine(adler, P->hres[k2]->adler, clen[k2]);
         if (cb) {
             const int e = cb(user, c, clen[k2], off);
             if (e) return e;
@@ -694,8 +707,8 @@ static int encode_fd_on(int device, int fd_in, int fd_out, const dmx_opts* opts,
     if (wstarted) pthread_join(wt, NULL);
     if (!r) r = S.err;
     if (!r && fd_out >= 0) {
-        const uint8_t tail[4] = {(uint8_t)(adler >> 24), (uint8_t)(adler >> 16), (uint8_t)(adler >> 8), (uint8_t)adler};
-        r = write_full(fd_out, tail, 4);
+        uint8_t tail[8];
+        r = write_full(fd_out, tail, stream_trailer(tail, gz, adler, nin_total));
     }
     if (R.seekable) (void)lseek(fd_in, (off_t)R.off, SEEK_SET);   // consumed, as read() would leave it
     // nothing may still run on the cached buffers when the lock is released
@@ -706,7 +719,7 @@ static int encode_fd_on(int device, int fd_in, int fd_out, const dmx_opts* opts,
         pthread_mutex_lock(&g_fd_last_mu);
         g_fd_last.chunks = nchunks;
         g_fd_last.bytes_in = nin_total;
-        g_fd_last.bytes_out = nout_total + 4;
+        g_fd_last.bytes_out = nout_total + (gz ? 8 : 4);
         g_fd_last.wall_ms = fd_now_ms() - t_begin;
         g_fd_last.read_ms = S.read_ms;
         g_fd_last.h2d_ms = h2d_ms;
@@ -803,7 +816,7 @@ static void* multi_worker(void* a) {
     MultiJob* J = W->J;
     dmx_ctx* c = W->c;
     if (hip_fail(hipSetDevice(c->device), "hipSetDevice")) { multi_fail(J, -(int)E_DEVICE); return NULL; }
-    const uint64_t ocap = dmx_max_compressed(J->chunk, (int32_t)J->sw);
+    const uint64_t ocap = dmx_max_compressed_flags(J->chunk, (int32_t)J->sw, J->pflags);
     const uint64_t step = (uint64_t)J->ndev;
     auto chunk_len = [&](uint64_t i) {
         const uint64_t lo = i * J->chunk, left = J->size - J->off0 - lo;
@@ -833,7 +846,8 @@ static void* multi_worker(void* a) {
         while (J->next != i && !J->err) pthread_cond_wait(&J->cv, &J->mu);
         if (!J->err) {
             if (J->fd_out >= 0) r = write_full(J->fd_out, c->fd_hout[k], olen);
-            J->adler = dmx_adler32_combine(J->adler, cadl, len);
+            J->adler = (J->pflags & DMX_F_GZIP) ? dmx_crc32_combine(J->adler, cadl, len)
+                                                : dmx_adler32_combine(J->adler, cadl, len);
             if (r) J->err = r;
             J->next = i + 1;
         }
@@ -902,17 +916,18 @@ extern "C" int dmx_encode_fd_multi(int fd_in, int fd_out, const dmx_opts* opts, 
     J.nchunks = (J.size - J.off0 + chunk - 1) / chunk;
     if (J.nchunks == 0) J.nchunks = 1;   // an empty input is one empty chunk (header, EOB block, trailer)
     J.o = o;
-    J.pflags = o.flags & (DMX_F_LAZY | DMX_F_SPLIT | DMX_F_DICT | DMX_F_EXACT_SORT | DMX_F_STORE_CHECK | DMX_F_DEEP);
+    J.pflags = o.flags & (DMX_F_LAZY | DMX_F_SPLIT | DMX_F_DICT | DMX_F_EXACT_SORT | DMX_F_STORE_CHECK | DMX_F_DEEP |
+                          DMX_F_GZIP);
     J.ndev = ndev < (int)J.nchunks ? ndev : (int)J.nchunks;
     pthread_mutex_init(&J.mu, NULL);
     pthread_cond_init(&J.cv, NULL);
     J.next = 0;
-    J.adler = 1;
+    J.adler = (J.pflags & DMX_F_GZIP) ? 0u : 1u;
     J.err = 0;
     pthread_mutex_lock(&g_mu);
     int r = 0;
     MultiWorker W[64];
-    const uint64_t ocap = dmx_max_compressed(chunk, o.sw);
+    const uint64_t ocap = dmx_max_compressed_flags(chunk, o.sw, J.pflags);
     for (int w = 0; w < J.ndev && !r; w++) {   // the workers' contexts (cached per list position)
         if (g_wctx[w] && g_wctx[w]->device != devices[w]) {
             dmx_ctx_destroy(g_wctx[w]);
@@ -934,9 +949,8 @@ extern "C" int dmx_encode_fd_multi(int fd_in, int fd_out, const dmx_opts* opts, 
         if (started[w]) pthread_join(th[w], NULL);
     if (!r) r = J.err;
     if (!r && fd_out >= 0) {
-        const uint32_t ad = J.adler;
-        const uint8_t tail[4] = {(uint8_t)(ad >> 24), (uint8_t)(ad >> 16), (uint8_t)(ad >> 8), (uint8_t)ad};
-        r = write_full(fd_out, tail, 4);
+        uint8_t tail[8];
+        r = write_full(fd_out, tail, stream_trailer(tail, (J.pflags & DMX_F_GZIP) != 0, J.adler, J.size - J.off0));
     }
     if (!r) (void)lseek(fd_in, (off_t)J.size, SEEK_SET);   // consumed, as read() would leave it
     for (int w = 0; w < J.ndev; w++)   // an error may have left copies in flight from the cached buffers

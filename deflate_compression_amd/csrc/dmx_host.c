@@ -18,6 +18,7 @@
 #include <unistd.h>
 
 #include "../../include/dmx.h"
+#include "dmx_crc.h"
 #include "dmx_internal.h"
 
 /* from dmx_kernels.hip */
@@ -178,11 +179,15 @@ int deflate_compress(int fd_in, int fd_out, int fd_stats, swi sw, int ops) {
         if (mode && *mode && strcmp(mode, "exact") != 0 && strcmp(mode, "ref") != 0) return -E_INVAL;
         exact = mode && strcmp(mode, "exact") == 0;
     }
+    /* DMX_FORMAT: the container -- unset / "zlib" the zlib stream, "gzip" one gzip member
+     * (DMX_F_GZIP); anything else fails before anything is read or written */
+    const char* fm = getenv("DMX_FORMAT");
+    if (fm && *fm && strcmp(fm, "zlib") != 0 && strcmp(fm, "gzip") != 0) return -E_INVAL;
     const char* mc = getenv("DMX_MAX_CHAIN");
     dmx_opts o;
     o.sw = swv;
     o.max_chain = mc ? atoi(mc) : 0;
-    o.flags = DMX_ZLIB;
+    o.flags = (fm && strcmp(fm, "gzip") == 0) ? DMX_GZIP : DMX_ZLIB;
     const char* lz = getenv("DMX_LAZY");   /* 1 = lazy evaluation (DMX_F_LAZY); default greedy */
     if (lz && atoi(lz) > 0) o.flags |= DMX_F_LAZY;
     const char* sp = getenv("DMX_SPLIT");  /* 1 = adaptive block splitting (DMX_F_SPLIT) */
@@ -235,4 +240,10 @@ uint32_t dmx_adler32_combine(uint32_t a, uint32_t b, uint64_t len_b) {
     s1 = (s1 + (b & 0xFFFF) + M - 1) % M;
     s2 = (s2 + ((a >> 16) & 0xFFFF) + ((b >> 16) & 0xFFFF) + M - rem) % M;
     return (uint32_t)(s1 | (s2 << 16));
+}
+
+/* CRC-32 of A||B from crc(A), crc(B) and len(B): crc(A) x^(8 len(B)) xor crc(B) -- the init and
+ * final-xor terms of the two values cancel (dmx_crc.h). */
+uint32_t dmx_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) {
+    return dmx_gf2_mulmod(dmx_gf2_xpow(len_b, 3), crc_a) ^ crc_b;
 }

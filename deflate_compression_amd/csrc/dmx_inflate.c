@@ -22,6 +22,7 @@
 #include <string.h>
 
 #include "../../include/dmx.h"
+#include "dmx_crc.h"
 
 #define MAXBITS 15
 #define FAST 9
@@ -252,6 +253,65 @@ static uint32_t adler32(const uint8_t* d, size_t n) {
     return (b << 16) | a;
 }
 
+/* CRC-32 (RFC 1952 §8), slice-by-4 tables built on first use (idempotent: every thread that
+ * races writes the same values; the ready flag is published last). */
+static uint32_t g_crc_tab[4][256];
+static int g_crc_ready;
+uint32_t dmx_crc32_host(uint32_t crc, const uint8_t* d, uint64_t n) {
+    if (!__atomic_load_n(&g_crc_ready, __ATOMIC_ACQUIRE)) {
+        for (uint32_t b = 0; b < 256; b++) {
+            uint32_t c = b;
+            for (int k = 0; k < 8; k++) c = (c >> 1) ^ ((0u - (c & 1u)) & DMX_CRC_POLY);
+            g_crc_tab[0][b] = c;
+        }
+        for (int k = 1; k < 4; k++)
+            for (uint32_t b = 0; b < 256; b++)
+                g_crc_tab[k][b] = (g_crc_tab[k - 1][b] >> 8) ^ g_crc_tab[0][g_crc_tab[k - 1][b] & 0xFFu];
+        __atomic_store_n(&g_crc_ready, 1, __ATOMIC_RELEASE);
+    }
+    uint32_t c = ~crc;
+    while (n >= 4) {
+        c ^= (uint32_t)d[0] | ((uint32_t)d[1] << 8) | ((uint32_t)d[2] << 16) | ((uint32_t)d[3] << 24);
+        c = g_crc_tab[3][c & 0xFFu] ^ g_crc_tab[2][(c >> 8) & 0xFFu] ^ g_crc_tab[1][(c >> 16) & 0xFFu] ^ g_crc_tab[0][c >> 24];
+        d += 4;
+        n -= 4;
+    }
+    while (n--) c = g_crc_tab[0][(c ^ *d++) & 0xFFu] ^ (c >> 8);
+    return ~c;
+}
+
+/* The gzip member header (RFC 1952 §2.3) at in[0..n): ID1 ID2 CM FLG MTIME(4) XFL OS, then
+ * FEXTRA (XLEN + bytes), FNAME and FCOMMENT (zero-terminated), FHCRC (2 bytes, not checked).
+ * Returns the offset of the DEFLATE data, or -E_* (a header cut short: -E_ZHEAD). */
+static long gzip_header(const uint8_t* in, size_t n, size_t* body) {
+    if (n < 3) return -(long)E_ZHEAD;
+    if (in[2] != 8) return -(long)E_ZCMPMT;
+    if (n < 4) return -(long)E_ZHEAD;
+    const int flg = in[3];
+    if (flg & 0xE0) return -(long)E_RESERV;
+    if (n < 10) return -(long)E_ZHEAD;
+    size_t p = 10;
+    if (flg & 4) {   /* FEXTRA */
+        if (n - p < 2) return -(long)E_ZHEAD;
+        const size_t xlen = (size_t)in[p] | ((size_t)in[p + 1] << 8);
+        p += 2;
+        if (n - p < xlen) return -(long)E_ZHEAD;
+        p += xlen;
+    }
+    for (int f = 8; f <= 16; f <<= 1) {   /* FNAME, FCOMMENT */
+        if (!(flg & f)) continue;
+        while (p < n && in[p]) p++;
+        if (p >= n) return -(long)E_ZHEAD;
+        p++;
+    }
+    if (flg & 2) {   /* FHCRC */
+        if (n - p < 2) return -(long)E_ZHEAD;
+        p += 2;
+    }
+    *body = p;
+    return 0;
+}
+
 int deflate_decompress(struct string_len* decompr_dat, struct string_len* compr_dat, int ops) {
     if (!decompr_dat || !compr_dat || (!compr_dat->str && compr_dat->len)) return -E_INVAL;
     ist s;
@@ -262,11 +322,19 @@ int deflate_decompress(struct string_len* decompr_dat, struct string_len* compr_
     decompr_dat->len = 0;
     if (s.n < 2) return -(int)E_ZHEAD;
     const int cmf = s.in[0], flg = s.in[1];
-    if ((cmf & 0x0F) != 8) return -(int)E_ZCMPMT;
-    if ((cmf >> 4) > 7) return -(int)E_ZSLWIN;
-    if (((cmf << 8) | flg) % 31) return -(int)E_ZFCHCK;
-    if (flg & 0x20) return -(int)E_ZPDICT;
-    s.pos = 2;
+    const int gz = cmf == 0x1F && flg == 0x8B;   /* a gzip member (as zlib it would be CM 15) */
+    if (gz) {
+        size_t body = 0;
+        const long e = gzip_header(s.in, s.n, &body);
+        if (e) return (int)e;
+        s.pos = body;
+    } else {
+        if ((cmf & 0x0F) != 8) return -(int)E_ZCMPMT;
+        if ((cmf >> 4) > 7) return -(int)E_ZSLWIN;
+        if (((cmf << 8) | flg) % 31) return -(int)E_ZFCHCK;
+        if (flg & 0x20) return -(int)E_ZPDICT;
+        s.pos = 2;
+    }
     int last, r = 0;
     do {
         last = bits(&s, 1);
@@ -278,7 +346,18 @@ int deflate_decompress(struct string_len* decompr_dat, struct string_len* compr_
         else r = -(int)E_ZBTYPE;
         if (r) break;
     } while (!last);
-    if (!r) {
+    if (!r && gz) {
+        /* drop the partial byte, then CRC-32 and ISIZE, little-endian; a trailer cut short
+         * is -E_CRC; bytes after the member are ignored */
+        s.bitbuf >>= s.bitcnt & 7;
+        s.bitcnt -= s.bitcnt & 7;
+        uint32_t want = 0, isize = 0;
+        for (int k = 0; k < 4; k++) want |= (uint32_t)bits(&s, 8) << (8 * k);
+        for (int k = 0; k < 4; k++) isize |= (uint32_t)bits(&s, 8) << (8 * k);
+        if (s.err) r = -(int)E_CRC;
+        else if (want != dmx_crc32_host(0, s.out, s.olen)) r = -(int)E_CRC;
+        else if (isize != (uint32_t)s.olen) r = -(int)E_LEN;
+    } else if (!r) {
         /* drop the partial byte, then the big-endian Adler-32 */
         s.bitbuf >>= s.bitcnt & 7;
         s.bitcnt -= s.bitcnt & 7;

@@ -2305,6 +2305,15 @@ __device__ __forceinline__ bool wl_skip(uint32_t x, uint32_t M, uint32_t nblk) {
 // occupy, at their speculative offsets (the true ones inside the stored prefix); empty when
 // there are none.  Nothing after K0 may write there: the apply launch zeroes the words the
 // other blocks share around that range byte by byte (zero_word_keep).
+// The container's framing widths: the zlib header 78 9C (16 bits) and big-endian Adler-32
+// (32), or with DMX_F_GZIP the 10-byte gzip header (80) and CRC-32 + ISIZE (64).  80 = 16 mod 32,
+// so the first block starts at the same bit of a word in both, two words later.
+__host__ __device__ __forceinline__ uint32_t hdr_bits(uint32_t flags) {
+    return !(flags & DMX_F_HEADER) ? 0u : (flags & DMX_F_GZIP) ? 80u : 16u;
+}
+__host__ __device__ __forceinline__ uint32_t trl_bits(uint32_t flags) {
+    return !(flags & DMX_F_TRAILER) ? 0u : (flags & DMX_F_GZIP) ? 64u : 32u;
+}
 __device__ __forceinline__ uint64_t spec_stored_bit(uint32_t b, uint32_t sw, uint32_t flags);
 __device__ __forceinline__ void wl_prefix_bytes(uint32_t M, uint32_t nblk, uint32_t sw, uint32_t flags,
                                                 uint64_t& A, uint64_t& P) {
@@ -2336,7 +2345,7 @@ __device__ __forceinline__ void zero_word_keep(uint32_t* out32, uint64_t w, uint
 // all of its words, so a misplaced quad inside the stream is overwritten (words shared
 // between blocks are zeroed by the scan first), and one past the stream's end is outside it.
 __device__ __forceinline__ uint64_t spec_stored_bit(uint32_t b, uint32_t sw, uint32_t flags) {
-    return ((flags & DMX_F_HEADER) ? 16ull : 0ull) + 8ull * (uint64_t)b * ((uint64_t)sw + 5);
+    return (uint64_t)hdr_bits(flags) + 8ull * (uint64_t)b * ((uint64_t)sw + 5);
 }
 // the stored block's 16-byte output quads with a whole 20-byte input window (the pack
 // kernel's fast path); calls f(k, o0) for every such quad: output word gw0 + k, input offset o0
@@ -4577,15 +4586,33 @@ __device__ __forceinline__ void gor_bits(uint32_t* out32, uint64_t pos, uint32_t
     if (sh + nb > 32) atomicOr(&out32[w + 1], v >> (32 - sh));
 }
 
-// zlib header (bits 0..15), the sync flush after a non-final shard's last block, the
-// Adler-32 trailer; T = end of the last block, end = byte-aligned end of the DEFLATE data.
+// The container header: zlib 78 9C (bits 0..15), or gzip 1F 8B 08 00, mtime 0, XFL 0, OS 255
+// (bits 0..79).  The gzip header owns words 0 and 1 (plain stores: nothing else writes them) and
+// shares word 2 with the first block, as the zlib header shares word 0 (zeroed by the scan).
+__device__ __forceinline__ void put_header(uint32_t* out32, uint32_t flags) {
+    if (!(flags & DMX_F_HEADER)) return;
+    if (flags & DMX_F_GZIP) {
+        out32[0] = 0x00088B1Fu;
+        out32[1] = 0u;
+        gor_bits(out32, 64, 0xFF00u, 16);
+    } else {
+        gor_bits(out32, 0, 0x9C78u, 16);
+    }
+}
+
+// the header, the sync flush after a non-final shard's last block, the trailer (big-endian
+// Adler-32, or with DMX_F_GZIP little-endian CRC-32 and input length n mod 2^32; `adler` is
+// the stream's check value, either one); T = end of the last block, end = byte-aligned end of the DEFLATE data.
 __device__ __forceinline__ void stream_framing(uint32_t* out32, uint32_t flags, uint32_t nblk, uint64_t T,
-                                               uint64_t end, uint32_t adler) {
-    const uint64_t start = (flags & DMX_F_HEADER) ? 16 : 0;
-    if (flags & DMX_F_HEADER) gor_bits(out32, 0, 0x9C78u, 16);
+                                               uint64_t end, uint32_t adler, uint64_t n) {
+    const uint64_t start = hdr_bits(flags);
+    put_header(out32, flags);
     if (nblk == 0 && (flags & DMX_F_FINAL)) gor_bits(out32, start, 3u, 3);  // BFINAL=1, BTYPE=01, EOB=0000000
     if (!(flags & DMX_F_FINAL) && nblk > 0) gor_bits(out32, align8(T + 3) + 16, 0xFFFFu, 16);  // sync flush
-    if (flags & DMX_F_TRAILER) {
+    if ((flags & DMX_F_TRAILER) && (flags & DMX_F_GZIP)) {
+        gor_bits(out32, end, adler, 32);
+        gor_bits(out32, end + 32, (uint32_t)n, 32);
+    } else if (flags & DMX_F_TRAILER) {
         const uint32_t a = adler;
         const uint32_t be = (a >> 24) | ((a >> 8) & 0xFF00u) | ((a << 8) & 0xFF0000u) | (a << 24);
         gor_bits(out32, end, be, 32);
@@ -4607,7 +4634,8 @@ __device__ __forceinline__ void stream_framing(uint32_t* out32, uint32_t flags, 
 //                          last block; an empty input gets its whole stream here;
 //   dmx_scan_apply_kernel  per tile: absolute offsets, and zero the words each block shares
 //                          with a neighbour (the pack kernel ORs those).
-// The zlib header, sync flush and trailer are ORed by the pack kernel (first/last block).
+// The container header (zlib or gzip), sync flush and trailer are written by the pack kernel
+// (first/last block; put_header, stream_framing).
 struct ScanTile {
     uint64_t a, c, s;                      // aggregate Mono (s: has a stored block)
     uint64_t ps, pa, pc;                   // exclusive prefix over the tiles before
@@ -4701,13 +4729,14 @@ __global__ __launch_bounds__(SCAN_TILE) void dmx_scan_tile_kernel(dmx_blkinfo* _
 __global__ __launch_bounds__(ST) void dmx_scan_kernel(ScanTile* __restrict__ tiles, uint32_t nblk, uint64_t n,
                                                       uint32_t flags, uint64_t out_cap,
                                                       uint32_t* __restrict__ out32, dmx_result* __restrict__ res,
-                                                      uint32_t* __restrict__ nfallback, uint32_t* __restrict__ hint) {
+                                                      uint32_t* __restrict__ nfallback, uint32_t* __restrict__ hint,
+                                                      const uint32_t* __restrict__ crc) {
     __shared__ Mono wtot[ST / 64];
     __shared__ uint32_t kcnt[4];
     __shared__ Mono carry_s;
     __shared__ uint64_t red[ST / 64][5];
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint64_t start = (flags & DMX_F_HEADER) ? 16 : 0;
+    const uint64_t start = hdr_bits(flags);
     const uint32_t ntile = (nblk + SCAN_TILE - 1) / SCAN_TILE;
     uint64_t adl_s1 = 0, adl_s2 = 0, ntok = 0, nsto = 0, nfix = 0;
     uint32_t k0 = 0, k2 = 0, k3 = 0, ku = 0;
@@ -4781,11 +4810,12 @@ __global__ __launch_bounds__(ST) void dmx_scan_kernel(ScanTile* __restrict__ til
         for (int w = 0; w < ST / 64; w++) { s1 += red[w][0]; s2 += red[w][1]; nt += red[w][2]; ns += red[w][3]; nf += red[w][4]; }
         s1 = (1 + s1) % ADL_MOD;
         s2 = (n % ADL_MOD + s2) % ADL_MOD;
-        const uint32_t adler = (uint32_t)((s2 << 16) | s1);
+        // the stream's check value: Adler-32, or the CRC-32 the CRC launches left (DMX_F_GZIP)
+        const uint32_t adler = crc ? crc[0] : (uint32_t)((s2 << 16) | s1);
         uint64_t T = mapply(carry_s, start);
         if (nblk == 0 && (flags & DMX_F_FINAL)) T = start + 10;   // empty input: fixed block, EOB only
         uint64_t end = (flags & DMX_F_FINAL) ? align8(T) : (nblk == 0 ? align8(T) : align8(T + 3) + 32);
-        uint64_t out_len = end / 8 + ((flags & DMX_F_TRAILER) ? 4 : 0);
+        uint64_t out_len = end / 8 + trl_bits(flags) / 8;
         int32_t status = 0;
         if (((out_len + 3) & ~3ull) > out_cap) status = -(int32_t)E_SZ;
         res->out_len = out_len;
@@ -4818,15 +4848,15 @@ __global__ __launch_bounds__(ST) void dmx_scan_kernel(ScanTile* __restrict__ til
     if (s_status) return;
     // zero the words past the last block (the framing goes there)
     const uint64_t T = s_T, end = s_end;
-    const uint64_t tail_end = end + ((flags & DMX_F_TRAILER) ? 32 : 0);
+    const uint64_t tail_end = end + trl_bits(flags);
     // (word T >> 5, when the last block ends inside it, is that block's last word: the apply
     // launch zeroes it, keeping any bytes of the whole-copy prefix it holds)
     const uint64_t tw0 = nblk ? (T + 31) >> 5 : T >> 5;
     for (uint64_t w = tw0 + tid; w < ((tail_end + 31) >> 5); w += ST) out32[w] = 0;
     if (nblk == 0) {   // no pack launch: the whole stream is written here
-        if (tid == 0 && start) out32[0] = 0;
+        if (tid <= (start >> 5) && start) out32[tid] = 0;   // every word the header touches (T >> 5 is at or past the last)
         __syncthreads();
-        if (tid == 0) stream_framing(out32, flags, 0, T, end, s_adler);
+        if (tid == 0) stream_framing(out32, flags, 0, T, end, s_adler, n);
     }
 }
 
@@ -4839,7 +4869,7 @@ __global__ __launch_bounds__(SCAN_TILE) void dmx_scan_apply_kernel(dmx_blkinfo* 
     if (res->status) return;
     const uint32_t b = blockIdx.x * SCAN_TILE + threadIdx.x;
     if (b >= nblk) return;
-    const uint64_t start = (flags & DMX_F_HEADER) ? 16 : 0;
+    const uint64_t start = hdr_bits(flags);
     const ScanTile& T = tiles[blockIdx.x];
     Mono tp, lp;
     tp.s = (uint32_t)T.ps; tp.a = T.pa; tp.c = T.pc;
@@ -4851,7 +4881,7 @@ __global__ __launch_bounds__(SCAN_TILE) void dmx_scan_apply_kernel(dmx_blkinfo* 
     info[b].off_bits = o;
     info[b].len_bits = l;
     if (!wl) {
-        out32[o >> 5] = 0;            // shared with the block before (or the zlib header)
+        out32[o >> 5] = 0;            // shared with the block before (or the container header: word 0, gzip word 2)
         out32[(o + l - 1) >> 5] = 0;  // shared with the block after (or the framing)
         return;
     }
@@ -4884,14 +4914,15 @@ __global__ __launch_bounds__(SCAN_TILE) void dmx_scan_apply1_kernel(dmx_blkinfo*
                                                                    uint32_t* __restrict__ out32, dmx_result* __restrict__ res,
                                                                    uint32_t* __restrict__ nfallback, uint32_t* __restrict__ hint,
                                                                    uint32_t* __restrict__ wl, uint32_t* __restrict__ L4,
-                                                                   const uint16_t* __restrict__ codes) {
+                                                                   const uint16_t* __restrict__ codes,
+                                                                   const uint32_t* __restrict__ crc) {
     __shared__ Mono wt[SCAN_TILE / 64];
     __shared__ Mono s_pre;
     __shared__ uint64_t red[SCAN_TILE / 64][9];
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t ntile = (nblk + SCAN_TILE - 1) / SCAN_TILE, tt = blockIdx.x;
     const bool lastwg = tt + 1 == ntile;
-    const uint64_t start = (flags & DMX_F_HEADER) ? 16 : 0;
+    const uint64_t start = hdr_bits(flags);
     // thread i composes tiles [i C, i C + C) in order; the one holding tile tt notes the part before it
     const uint32_t C = (ntile + SCAN_TILE - 1) / SCAN_TILE;
     const uint32_t t0 = tid * C < ntile ? tid * C : ntile, t1 = t0 + C < ntile ? t0 + C : ntile;
@@ -4939,7 +4970,7 @@ __global__ __launch_bounds__(SCAN_TILE) void dmx_scan_apply1_kernel(dmx_blkinfo*
     // the stream's end and status (every workgroup: nothing is written past out_cap)
     const uint64_t T = mapply(tot, start);
     const uint64_t end = (flags & DMX_F_FINAL) ? align8(T) : align8(T + 3) + 32;
-    const uint64_t out_len = end / 8 + ((flags & DMX_F_TRAILER) ? 4 : 0);
+    const uint64_t out_len = end / 8 + trl_bits(flags) / 8;
     const int32_t status = (((out_len + 3) & ~3ull) > out_cap) ? -(int32_t)E_SZ : 0;
     if (lastwg && tid == 0) {
         uint64_t a1 = 0, a2 = 0, ntk = 0, nst = 0, nfx = 0, q0 = 0, q2 = 0, q3 = 0, qu = 0;
@@ -4953,7 +4984,7 @@ __global__ __launch_bounds__(SCAN_TILE) void dmx_scan_apply1_kernel(dmx_blkinfo*
         res->end_bits = T;
         res->n = n;
         res->ntokens = ntk;
-        res->adler = (uint32_t)((a2 << 16) | a1);
+        res->adler = crc ? crc[0] : (uint32_t)((a2 << 16) | a1);   // (as dmx_scan_kernel)
         res->status = status;
         res->nblocks = nblk;
         res->nstored = (uint32_t)nst;
@@ -4973,7 +5004,7 @@ __global__ __launch_bounds__(SCAN_TILE) void dmx_scan_apply1_kernel(dmx_blkinfo*
     }
     if (status) return;
     if (lastwg) {   // zero the words past the last block (the framing goes there)
-        const uint64_t tail_end = end + ((flags & DMX_F_TRAILER) ? 32 : 0);
+        const uint64_t tail_end = end + trl_bits(flags);
         for (uint64_t w = ((T + 31) >> 5) + tid; w < ((tail_end + 31) >> 5); w += SCAN_TILE) out32[w] = 0;   // (as dmx_scan_kernel)
     }
     __syncthreads();   // (s_pre)
@@ -5034,15 +5065,15 @@ __device__ __forceinline__ void st_or64(uint32_t* st, uint32_t pos, uint64_t v, 
     if (sh + nb > 64) atomicOr(&st[w + 2], (uint32_t)(v >> (64 - sh)));
 }
 
-// The first block ORs the zlib header, the last one the sync flush / trailer (the scan
-// zeroed those words; every write into them is an atomicOr).
+// The first block writes the container header, the last one the sync flush / trailer (the
+// scan zeroed the words they share with a block; every write into those is an atomicOr).
 __device__ __forceinline__ void pack_framing(uint32_t* out32, uint32_t flags, uint32_t nblk, uint32_t b,
                                              const dmx_result* res) {
-    if (b == 0 && (flags & DMX_F_HEADER)) gor_bits(out32, 0, 0x9C78u, 16);
+    if (b == 0) put_header(out32, flags);
     if (b == nblk - 1) {
         const uint64_t T = res->end_bits;
         const uint64_t end = (flags & DMX_F_FINAL) ? align8(T) : align8(T + 3) + 32;
-        stream_framing(out32, flags & ~DMX_F_HEADER, nblk, T, end, res->adler);
+        stream_framing(out32, flags & ~DMX_F_HEADER, nblk, T, end, res->adler, res->n);
     }
 }
 
@@ -5103,7 +5134,8 @@ __device__ __forceinline__ void pack_one(const uint32_t b, const uint8_t* __rest
         const uint32_t ks = 4 - (uint32_t)(gw0 & 3);                      // first quad: (gw0 + ks) % 4 == 0, ks >= 1
         const uint32_t nq = (dal && nwords > ks + 1) ? (nwords - 1 - ks) >> 2 : 0;   // quads short of the last word
         // With the copy in place only the first two and the last two quads can need words of
-        // their own: quad j >= 2 starts at byte >= 36 > B0 (<= 9), and quad j <= nq - 3 ends
+        // their own: quad j >= 2 starts at byte >= 36 > B0 (<= 9; bytes from the block's first
+        // word, so the same behind the 2-byte zlib and the 10-byte gzip header), and quad j <= nq - 3 ends
         // >= 44 bytes before the block's end, so both take the fast path, which K0 wrote.
         const uint32_t nqv = spec ? (nq < 4 ? nq : 4u) : nq;
         for (uint32_t t = tid; t < nqv; t += PT) {
@@ -5348,6 +5380,11 @@ __global__ __launch_bounds__(PT) void dmx_pack_kernel(const uint8_t* __restrict_
 
 #include "dmx_ctx.h"
 
+// CRC-32 of a device buffer (DMX_F_GZIP's check value, dmx_crc32_async): its kernels and their
+// launches have a file of their own, compiled into this translation unit -- every link of the
+// encode, whatever objects it lists, then has them.
+#include "dmx_crc.hip"
+
 
 // ---- fault injection (tests): DMX_FAULT="malloc:N" makes the N-th device / pinned allocation
 // from now fail, "launch:N" the N-th encode launch check; dmx_fault_set() sets it at run time.
@@ -5408,6 +5445,10 @@ extern "C" uint64_t dmx_max_compressed(uint64_t n, int32_t sw) {
     const uint64_t nblk = (n + (uint64_t)sw - 1) / (uint64_t)sw;
     return ((n + 5 * nblk + 2 + 4 + 5 + 16) + 3) & ~3ull;
 }
+// the same for a container: DMX_F_GZIP frames with 18 bytes (10 + 8) where zlib has 6 (2 + 4)
+extern "C" uint64_t dmx_max_compressed_flags(uint64_t n, int32_t sw, uint32_t flags) {
+    return dmx_max_compressed(n, sw) + ((flags & DMX_F_GZIP) ? 12u : 0u);
+}
 
 static void ctx_free_ws(dmx_ctx* c) {
     if (c->dist) (void)hipFree(c->dist);
@@ -5419,6 +5460,9 @@ static void ctx_free_ws(dmx_ctx* c) {
     if (c->info) (void)hipFree(c->info);
     if (c->tiles) (void)hipFree(c->tiles);
     if (c->wl) (void)hipFree(c->wl);
+    if (c->crc_rem) (void)hipFree(c->crc_rem);
+    c->crc_rem = NULL;
+    c->crc_cap = 0;
     c->dist = NULL; c->tok = NULL; c->hist = NULL; c->codes = NULL; c->hdr = NULL; c->sub = NULL; c->info = NULL;
     c->tiles = NULL;
     c->wl = NULL;
@@ -5476,6 +5520,10 @@ static int ctx_reserve(dmx_ctx* c, uint64_t nblk) {
         const uint32_t hw[2] = {(uint32_t)hp, (uint32_t)(hp >> 32)};
         HIPCHK(hipMemcpy(c->wl + WL_HINT, hw, sizeof(hw), hipMemcpyHostToDevice));
     }
+    // CRC-32 (dmx_crc.hip): 4 bytes per span of DMX_BLK bytes (one more for an unaligned base);
+    // the word an encode's CRC lands in is nfb[2], which every context has
+    HIPCHK(dmx_malloc(&c->crc_rem, (cb + 2) * sizeof(uint32_t)));
+    c->crc_cap = cb + 2;
     c->cap_blocks = cb;
     return ctx_reserve_scratch(c);
 }
@@ -5665,6 +5713,9 @@ extern "C" int dmx_encode_async(dmx_ctx* c, const void* d_in, uint64_t n, void* 
     HIPCHK(hipSetDevice(c->device));
     // no allocation here (graph-capturable, no device-wide sync): the split / dictionary
     // scratch comes from dmx_ctx_reserve_flags
+    // DMX_F_GZIP: the CRC-32 scratch holds a remainder per span (a context that never reserved
+    // a block has none, and needs none for an empty input)
+    if ((o.flags & DMX_F_GZIP) && dmx_crc32_spans(d_in, n) > c->crc_cap) return -(int)E_SZ;
     if ((o.flags & DMX_F_SPLIT) && c->cap_split < nblk) return -(int)E_SZ;
     if ((o.flags & DMX_F_DICT) && c->cap_chain < (uint64_t)nblk + 1) return -(int)E_SZ;
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
@@ -5754,6 +5805,14 @@ extern "C" int dmx_encode_async(dmx_ctx* c, const void* d_in, uint64_t n, void* 
         for (int k = 1; k <= 3; k++)
             if ((c->timing >> k) & 1) (void)hipEventRecord(ev[k], s);
     }
+    // DMX_F_GZIP: the stream's check value is the CRC-32 of the input, left in a device word
+    // by two launches of dmx_crc.hip that K3 reads (also without DMX_F_TRAILER: dmx_result
+    // reports it to whoever joins the shards)
+    const uint32_t* crcw = NULL;
+    if (o.flags & DMX_F_GZIP) {
+        crcw = c->nfb + 2;
+        dmx_crc32_launch(c, d_in, n, c->nfb + 2, s);   // (its capacity was checked above)
+    }
     const uint32_t ntile = (nblk + SCAN_TILE - 1) / SCAN_TILE;
     if (nblk)
         hipLaunchKernelGGL(dmx_scan_tile_kernel, dim3(ntile), dim3(SCAN_TILE), 0, s, c->info, nblk, n, (uint32_t)o.sw,
@@ -5762,10 +5821,10 @@ extern "C" int dmx_encode_async(dmx_ctx* c, const void* d_in, uint64_t n, void* 
     uint32_t* hintp = (!wl && (o.flags & DMX_F_STORE_CHECK)) ? c->whint_dev : NULL;
     if (nblk && ntile <= SA1_MAXT && !c->hk_scan3) {   // (hk_scan3: the three-launch scan at any size, tests)
         hipLaunchKernelGGL(dmx_scan_apply1_kernel, dim3(ntile), dim3(SCAN_TILE), 0, s, c->info, nblk, n, o.flags, out_cap,
-                           (uint32_t)o.sw, (const ScanTile*)c->tiles, (uint32_t*)d_out, c->res, c->nfb, hintp, wl, L4, dupk);
+                           (uint32_t)o.sw, (const ScanTile*)c->tiles, (uint32_t*)d_out, c->res, c->nfb, hintp, wl, L4, dupk, crcw);
     } else {
         hipLaunchKernelGGL(dmx_scan_kernel, dim3(1), dim3(ST), 0, s, c->tiles, nblk, n, o.flags, out_cap,
-                           (uint32_t*)d_out, c->res, c->nfb, hintp);
+                           (uint32_t*)d_out, c->res, c->nfb, hintp, crcw);
         if (nblk)
             hipLaunchKernelGGL(dmx_scan_apply_kernel, dim3(ntile), dim3(SCAN_TILE), 0, s, c->info, nblk, o.flags, (uint32_t)o.sw, c->tiles,
                                (uint32_t*)d_out, (const dmx_result*)c->res, wl, L4, dupk);

@@ -2,7 +2,8 @@
 
 Blocks are independent, so rank r of N encodes a contiguous, block-aligned range
 of the input with no collective on the data path.  Shard framing makes the pieces
-concatenable: rank 0 writes the zlib header, every non-final shard ends with an
+concatenable: rank 0 writes the zlib header (the gzip one with DMX_F_GZIP, whose trailer
+is combine_crc32 / trailer_gzip), every non-final shard ends with an
 empty stored block (sync flush, byte-aligned), the last shard carries BFINAL; the
 Adler-32 trailer is combined on the host from the per-shard Adler values
 (RFC 1950 arithmetic, dmx_adler32_combine).  The exchange step is a gather of the
@@ -17,7 +18,7 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
-from . import DMX_F_FINAL, DMX_F_HEADER, adler32_combine
+from . import DMX_F_FINAL, DMX_F_HEADER, adler32_combine, crc32_combine
 
 BLOCK = 32768
 
@@ -43,6 +44,19 @@ def combine_adler(adlers, lengths) -> int:
 
 def trailer(adler: int) -> bytes:
     return int(adler).to_bytes(4, "big")
+
+
+def combine_crc32(crcs, lengths) -> int:
+    """The CRC-32 of the whole input from the shards' (DMX_F_GZIP: Result.adler of each)."""
+    c = 0
+    for cr, ln in zip(crcs, lengths):
+        c = crc32_combine(c, int(cr), int(ln))
+    return c
+
+
+def trailer_gzip(crc: int, total_len: int) -> bytes:
+    """The gzip trailer: CRC-32, then the input length mod 2^32, little-endian."""
+    return (int(crc) & 0xFFFFFFFF).to_bytes(4, "little") + (int(total_len) & 0xFFFFFFFF).to_bytes(4, "little")
 
 
 def gather_chunks(chunk: torch.Tensor, length: int, root: int | None = 0, group=None):

@@ -42,7 +42,10 @@ void deflate_compr_init(deflate_compr_t* com, int fd_in, int fd_out, int fd_stat
 void deflate_compr_deinit(deflate_compr_t* com);
 
 /* deflate_ext.h:17, impl deflate_compress.c:362-376.
- * Reads fd_in to EOF, writes a zlib stream (RFC 1950/1951) to fd_out, and if
+ * Reads fd_in to EOF, writes a zlib stream (RFC 1950/1951) to fd_out -- or, with
+ * DMX_FORMAT=gzip in the environment, one gzip member (RFC 1952) around the same DEFLATE
+ * data; unset or "zlib" is the zlib stream, any other value returns -E_INVAL before anything
+ * is read or written -- and if
  * fd_stats >= 0 one 24-byte struct compress_stats per token.  sw = block size /
  * window (1..32768; 0 means 32768).  ops is unused (as in the reference).
  * The parse is the reference's: exhaustive hash-chain search, greedy, longest
@@ -54,7 +57,9 @@ int deflate_compress(int fd_in, int fd_out, int fd_stats, swi sw, int ops);
 
 /* deflate_ext.h:16, impl deflate_decompress.c:371-409 (that implementation does not
  * compile; this one is a fresh RFC 1950/1951 inflate).
- * Inflates compr_dat (zlib stream) into a malloc'd decompr_dat->str that the
+ * Inflates compr_dat (zlib stream, or a gzip member when it begins 1F 8B: optional
+ * FEXTRA / FNAME / FCOMMENT / FHCRC fields skipped, CRC-32 (-E_CRC) and ISIZE (-E_LEN)
+ * checked, bytes after the first member ignored) into a malloc'd decompr_dat->str that the
  * caller frees.  ops & DEFLATE_NULLTERM appends a '\0' (not counted in len).
  * Returns 0 or -E_*. */
 int deflate_decompress(struct string_len* decompr_dat, struct string_len* compr_dat, int ops);
@@ -123,13 +128,23 @@ struct compress_stats {
 
 /* ============================ Part 2: device layer ============================ */
 
-/* Stream framing flags (dmx_opts.flags). DMX_ZLIB = a complete zlib stream. */
-#define DMX_F_HEADER 1u  /* write the 2-byte zlib header 78 9C */
-#define DMX_F_TRAILER 2u /* write the Adler-32 trailer (big-endian) */
+/* Stream framing flags (dmx_opts.flags). DMX_ZLIB = a complete zlib stream, DMX_GZIP = a
+ * complete gzip member (RFC 1952). */
+#define DMX_F_HEADER 1u  /* write the container header: zlib 78 9C (2 bytes); with DMX_F_GZIP
+                            1F 8B 08 00 00 00 00 00 00 FF (10 bytes: no name, mtime 0, XFL 0,
+                            OS 255, so the output is deterministic) */
+#define DMX_F_TRAILER 2u /* write the trailer: Adler-32 big-endian (4 bytes); with DMX_F_GZIP
+                            CRC-32 then the input length mod 2^32, both little-endian (8 bytes) */
 #define DMX_F_FINAL 4u   /* last block carries BFINAL; otherwise the stream ends with
                             an empty stored block (sync flush) so it is byte-aligned
                             and another shard can be appended */
 #define DMX_ZLIB (DMX_F_HEADER | DMX_F_TRAILER | DMX_F_FINAL)
+#define DMX_F_GZIP 512u  /* container option: DMX_F_HEADER and DMX_F_TRAILER mean the gzip ones
+                            and the stream's check value is the CRC-32 of the input (computed on
+                            the device on the encode's stream, csrc/dmx_crc.hip), also when no
+                            trailer is written (shards: dmx_result.adler, dmx_crc32_combine).
+                            The DEFLATE data is bit for bit that of the zlib stream. */
+#define DMX_GZIP (DMX_ZLIB | DMX_F_GZIP)
 #define DMX_F_EXACT_SORT 16u  /* test hook: sort positions with the match-any grouping instead
                                 of lane-ordered LDS atomics (same result; used by the tests) */
 #define DMX_F_LAZY 8u    /* parse option: lazy evaluation, one position of
@@ -181,7 +196,8 @@ typedef struct {
     uint64_t end_bits;  /* bit position after the last block (before flush/trailer) */
     uint64_t n;         /* input bytes */
     uint64_t ntokens;   /* tokens over all blocks */
-    uint32_t adler;     /* Adler-32 of this input (RFC 1950 §8.2) */
+    uint32_t adler;     /* the stream's check value: Adler-32 of this input (RFC 1950 §8.2), or
+                           with DMX_F_GZIP its CRC-32 (RFC 1952 §8) */
     int32_t status;     /* 0 or -E_* */
     uint32_t nblocks;
     uint32_t nstored, nfixed, ndynamic;
@@ -206,6 +222,8 @@ int dmx_ctx_reserve(dmx_ctx* ctx, uint64_t n, int32_t sw);
 int dmx_ctx_reserve_flags(dmx_ctx* ctx, uint64_t n, int32_t sw, uint32_t flags);
 /* Worst-case output bytes for n input bytes with block size sw. */
 uint64_t dmx_max_compressed(uint64_t n, int32_t sw);
+/* The same for the container `flags` select: 12 bytes more under DMX_F_GZIP. */
+uint64_t dmx_max_compressed_flags(uint64_t n, int32_t sw, uint32_t flags);
 
 /* Enqueue the whole encode of device buffer d_in[0..n) into d_out (capacity
  * out_cap) on `stream` (hipStream_t; NULL = the context's stream).  No host
@@ -226,7 +244,7 @@ int dmx_encode_result(dmx_ctx* ctx, dmx_result* r, void* stream);
 int dmx_encode_result_async(dmx_ctx* ctx, dmx_result* r, void* stream);
 
 /* Host-buffer convenience (H2D, encode, D2H) on a cached per-device context.
- * *out_len receives the stream length; out must hold dmx_max_compressed(n, sw). */
+ * *out_len receives the stream length; out must hold dmx_max_compressed_flags(n, sw, flags). */
 int dmx_encode_host(const uint8_t* in, uint64_t n, uint8_t* out, uint64_t out_cap,
                     uint64_t* out_len, const dmx_opts* opts);
 
@@ -234,8 +252,10 @@ int dmx_encode_host(const uint8_t* in, uint64_t n, uint8_t* out, uint64_t out_ca
  * chunks of `chunk` bytes (rounded down to a multiple of sw; 0 = sw) into pinned memory,
  * encodes chunk i on the device while reading chunk i+1, writes one zlib stream to fd_out
  * (chunks joined by sync flushes, Adler-32 combined on the host; DMX_F_DICT carries the
- * history across chunks).  opts->flags: the parse/block options (DMX_F_LAZY, _SPLIT, _DICT);
- * the framing is its own.  Returns 0 or -E_*. */
+ * history across chunks).  opts->flags: the parse/block options (DMX_F_LAZY, _SPLIT, _DICT)
+ * and DMX_F_GZIP (one gzip member: chunk 0 carries the gzip header, the chunks' CRC-32s are
+ * combined on the host, which writes CRC-32 and the byte count mod 2^32 at the end); the rest
+ * of the framing is its own.  Returns 0 or -E_*. */
 int dmx_encode_fd(int fd_in, int fd_out, const dmx_opts* opts, uint64_t chunk);
 
 /* Where the last single-device dmx_encode_fd call (or deflate_compress without fd_stats)
@@ -362,6 +382,23 @@ int dmx_refest_feed(dmx_refest* e, const uint32_t* tok, uint32_t ntok, struct co
 
 /* Adler-32 combine (RFC 1950 math): adler of A||B from adler(A), adler(B), len(B). */
 uint32_t dmx_adler32_combine(uint32_t a, uint32_t b, uint64_t len_b);
+
+/* ---- CRC-32 (IEEE 802.3 / RFC 1952 §8; also PNG's chunk CRC), csrc/dmx_crc.hip ---- */
+/* Enqueue the CRC-32 of the device buffer d_in[0..n), any alignment, on `stream` (NULL = the
+ * context's); the value lands in the device word d_crc (4-byte aligned).  n == 0 gives 0.  Two
+ * launches, no allocation, no host synchronisation (graph-capturable).  The kernel loads whole
+ * 16-byte aligned groups: up to 15 bytes before d_in and after d_in + n, in the aligned
+ * groups that hold the first and the last byte, are read (and masked), never written -- a
+ * sub-buffer's neighbours must be readable memory, which bytes of the same 16-byte group
+ * are.  The scratch (4 bytes
+ * per 32 KiB) is the context's: -E_SZ when n is more than the context is reserved for
+ * (dmx_ctx_reserve), and calls that share a context -- DMX_F_GZIP encodes included -- must be
+ * ordered on one stream.  Returns 0 or -E_*. */
+int dmx_crc32_async(dmx_ctx* ctx, const void* d_in, uint64_t n, uint32_t* d_crc, void* stream);
+/* CRC-32 combine: crc of A||B from crc(A), crc(B), len(B).  Host only. */
+uint32_t dmx_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+/* The CRC kernel's geometry (tests): bytes per workgroup span and per lane slice. */
+void dmx_crc32_geometry(uint32_t* span, uint32_t* lane_slice);
 
 /* Seeded synthetic inputs for the bench/tests (host, deterministic). */
 void dmx_gen_text(uint8_t* buf, uint64_t n, uint64_t seed);    /* enwik-style wiki text */
