@@ -8,7 +8,9 @@ include/dmx.h).  This module is a thin ctypes layer:
         deflate_ext.h:17 / deflate_compress.c:362 -- 0 or -E_* (no exceptions, like C)
     deflate_decompress(data, ops=0) -> bytes
         deflate_ext.h:16 -- raises DeflateError(code) on a negative return
-    compress(data, sw=32768, max_chain=0) -> bytes        host buffer convenience (gzip=True: a .gz member)
+    compress(data, sw=32768, max_chain=0) -> bytes        host buffer convenience (gzip=True: a .gz member,
+                                                          bgzf=True: BGZF, a gzip member per block)
+    bgzf_index(z) / inflate_bgzf_gpu(z)                   a BGZF file's members, decoded in parallel on the GPU
     Encoder                                               device-resident encodes
 
 There is no CPU fallback: if libdmx.so is missing the import of this module fails,
@@ -23,7 +25,7 @@ import struct
 __all__ = [
     "DeflateError", "Opts", "Result", "Encoder", "lib", "compress", "deflate_compress",
     "deflate_decompress", "max_compressed", "adler32_combine", "gen_text", "gen_random",
-    "COMPRESS_STATS", "E", "DMX_F_HEADER", "DMX_F_TRAILER", "DMX_F_FINAL", "DMX_ZLIB", "DMX_F_LAZY", "DMX_F_EXACT_SORT", "DMX_F_SPLIT", "DMX_F_DICT", "DMX_F_STORE_CHECK", "DMX_F_DEEP", "DMX_F_GZIP", "DMX_GZIP", "crc32_combine", "crc32_geometry", "inflate_gpu", "inflate_gpu_chained", "ref_estimates",
+    "COMPRESS_STATS", "E", "DMX_F_HEADER", "DMX_F_TRAILER", "DMX_F_FINAL", "DMX_ZLIB", "DMX_F_LAZY", "DMX_F_EXACT_SORT", "DMX_F_SPLIT", "DMX_F_DICT", "DMX_F_STORE_CHECK", "DMX_F_DEEP", "DMX_F_GZIP", "DMX_GZIP", "DMX_F_BGZF", "DMX_BGZF", "crc32_combine", "crc32_geometry", "bgzf_index", "inflate_bgzf_gpu", "inflate_gpu", "inflate_gpu_chained", "ref_estimates",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -41,6 +43,8 @@ DMX_F_STORE_CHECK = 128
 DMX_F_DEEP = 256
 DMX_F_GZIP = 512
 DMX_GZIP = DMX_ZLIB | DMX_F_GZIP
+DMX_F_BGZF = 1024
+DMX_BGZF = DMX_F_BGZF | DMX_F_FINAL
 _M = 1 << 24
 # src/include/global_errors.h:24-35 and src/include/deflate_errors.h:9-22
 E = {
@@ -120,6 +124,8 @@ def lib() -> ctypes.CDLL:
         "dmx_max_compressed": ([u64, i32], u64),
         "dmx_max_compressed_flags": ([u64, i32, u32], u64),
         "dmx_crc32_async": ([vp, vp, u64, vp, vp], ctypes.c_int),
+        "dmx_crc32_blocks_async": ([vp, vp, u64, i32, vp, vp], ctypes.c_int),
+        "dmx_bgzf_index": ([vp, u64, vp, vp, u32, u32p, ctypes.POINTER(u64)], ctypes.c_int),
         "dmx_crc32_combine": ([u32, u32, u64], u32),
         "dmx_crc32_geometry": ([u32p, u32p], None),
         "dmx_fd_last_stats": ([ctypes.POINTER(FdStats)], ctypes.c_int),
@@ -185,15 +191,17 @@ def fd_last_stats() -> dict | None:
 
 
 def max_compressed(n: int, sw: int = 32768, flags: int = DMX_ZLIB) -> int:
-    """Worst-case stream bytes for n input bytes (12 more for the gzip container, DMX_F_GZIP)."""
+    """Worst-case stream bytes for n input bytes (12 more for the gzip container, DMX_F_GZIP;
+    26 more per block and 28 for the end-of-file member under DMX_F_BGZF)."""
     return int(lib().dmx_max_compressed_flags(n, sw, flags))
 
 
 def compress(data, sw: int = 32768, max_chain: int = 0, flags: int = DMX_ZLIB, lazy: bool = False,
              split: bool = False, dict: bool = False, pre=None, store_check: bool = False,
-             deep: bool = False, gzip: bool = False) -> bytes:
+             deep: bool = False, gzip: bool = False, bgzf: bool = False) -> bytes:
     """Encode a host buffer on the GPU; returns the zlib stream (or raw DEFLATE with flags;
-    gzip = a gzip member around the same DEFLATE data, DMX_F_GZIP).
+    gzip = a gzip member around the same DEFLATE data, DMX_F_GZIP; bgzf = a gzip member per
+    sw block and the end-of-file member, DMX_BGZF -- not with split or dict).
     lazy = f2 lazy parse (DMX_F_LAZY), split = f3 adaptive block splitting (DMX_F_SPLIT),
     dict = f1 cross-block dictionary (DMX_F_DICT; pre = the bytes before `data`),
     store_check = noise blocks stored without a parse (DMX_F_STORE_CHECK),
@@ -202,6 +210,8 @@ def compress(data, sw: int = 32768, max_chain: int = 0, flags: int = DMX_ZLIB, l
     p, n, keep = _buf(data)
     if gzip:
         flags |= DMX_F_GZIP
+    if bgzf:
+        flags |= DMX_BGZF
     cap = max_compressed(n, sw, flags)
     out = ctypes.create_string_buffer(cap)
     olen = ctypes.c_uint64(0)
@@ -257,6 +267,66 @@ def inflate_gpu(z, out_cap: int, index=None, nblk: int = 0, stream=None):
     status = int(np.frombuffer(h[:4].tobytes(), np.int32)[0])
     olen = int(np.frombuffer(h[8:16].tobytes(), np.uint64)[0])
     return out[:olen], status
+
+
+def bgzf_index(z):
+    """The members of a BGZF file in host memory (dmx_bgzf_index): (index, crcs, total) -- index
+    a uint8 numpy array of nblk x 24 B dmx_iblock records (one per member with data: the first
+    bit of its DEFLATE data, output offset and length), crcs the members' stored CRC-32s
+    (uint32[nblk]), total the decoded length.  Members of more than 32768 input bytes (htslib's
+    default blocks) raise DeflateError(-E_RANGE).  Pure host code: no GPU needed."""
+    import numpy as np
+    L = lib()
+    p, n, keep = _buf(z)
+    nb, tot = ctypes.c_uint32(0), ctypes.c_uint64(0)
+    r = L.dmx_bgzf_index(p, n, None, None, 0, ctypes.byref(nb), ctypes.byref(tot))
+    if r != 0 and r != -E["E_SZ"]:
+        raise DeflateError(r, "dmx_bgzf_index")
+    idx = np.zeros(max(nb.value, 1) * 24, np.uint8)
+    crc = np.zeros(max(nb.value, 1), np.uint32)
+    _check(L.dmx_bgzf_index(p, n, ctypes.c_void_p(idx.ctypes.data), ctypes.c_void_p(crc.ctypes.data), nb.value,
+                            ctypes.byref(nb), ctypes.byref(tot)), "dmx_bgzf_index")
+    del keep
+    return idx[:nb.value * 24], crc[:nb.value], int(tot.value)
+
+
+def inflate_bgzf_gpu(z, verify: bool = True, encoder=None):
+    """Inflate a BGZF file (host bytes) on the GPU, every member in parallel: the host index
+    (bgzf_index), inflate_gpu with it, and with `verify` the CRC-32 of every decoded member
+    (Encoder.crc32_blocks) compared on the device against the members' stored values --
+    DeflateError(-E_CRC) on a mismatch.  The per-block CRC needs equal-sized members (all but
+    the last with the same ISIZE): a file that is not raises ValueError unless verify=False.
+    encoder: an Encoder to run the CRC on (one is made otherwise).  Returns a uint8 CUDA tensor."""
+    import numpy as np
+    import torch
+    idx, crcs, total = bgzf_index(z)
+    nblk = crcs.size
+    dev = f"cuda:{encoder.device if encoder is not None else 0}"
+    if nblk == 0:
+        return torch.empty(0, dtype=torch.uint8, device=dev)
+    lens = idx.view(np.uint32).reshape(nblk, 6)[:, 4]
+    sw = int(lens[0])
+    uniform = bool((lens[:-1] == sw).all()) and int(lens[-1]) <= sw
+    if verify and not uniform:
+        raise ValueError("inflate_bgzf_gpu: members of different sizes cannot be verified (verify=False)")
+    b = bytes(z) if not isinstance(z, np.ndarray) else z
+    zt = torch.from_numpy(np.frombuffer(b, dtype=np.uint8).copy()).to(dev)
+    out, st = inflate_gpu(zt, total, torch.from_numpy(idx.copy()).to(dev), nblk)
+    if st:
+        raise DeflateError(st, "inflate_gpu")
+    if out.numel() != total:
+        raise DeflateError(-E["E_LEN"], "inflate_gpu")
+    if verify:
+        enc = encoder if encoder is not None else Encoder(0, max_input=1)
+        try:
+            got = enc.crc32_blocks(out, sw)
+        finally:
+            if encoder is None:
+                enc.close()
+        want = torch.from_numpy(crcs.view(np.int32).copy()).to(dev)
+        if not torch.equal(got, want):
+            raise DeflateError(-E["E_CRC"], "inflate_bgzf_gpu")
+    return out
 
 
 def inflate_gpu_chained(z, out_cap: int, index, nblk: int, stream=None, work=None):
@@ -414,6 +484,22 @@ class Encoder:
                                        ctypes.c_void_p(w.data_ptr()), ctypes.c_void_p(s)), "dmx_crc32_async")
         torch.cuda.synchronize(t.device)
         return int(w.item()) & 0xFFFFFFFF
+
+    def crc32_blocks(self, t, sw: int = 32768, stream=None):
+        """CRC-32 of every sw-byte block of a uint8 CUDA tensor (the last one may be short),
+        computed on the device (dmx_crc32_blocks_async): an int32 CUDA tensor of ceil(n / sw)
+        words (view as uint32 on the host).  The tensor's storage may start at any byte."""
+        import torch
+        n = t.numel()
+        nb = (n + sw - 1) // sw
+        w = torch.empty(max(nb, 1), dtype=torch.int32, device=t.device)
+        s = stream if stream is not None else torch.cuda.current_stream(t.device).cuda_stream
+        if not s:   # the default stream's handle is NULL, which selects the context's own stream
+            torch.cuda.synchronize(t.device)
+        _check(self._L.dmx_crc32_blocks_async(self._ctx, ctypes.c_void_p(t.data_ptr() if n else 0), n, sw,
+                                              ctypes.c_void_p(w.data_ptr()), ctypes.c_void_p(s)), "dmx_crc32_blocks_async")
+        torch.cuda.synchronize(t.device)
+        return w[:nb]
 
     # -- introspection of the last encode (tests / stats) --
     def blocks(self, nblk: int):

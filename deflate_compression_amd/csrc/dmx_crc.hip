@@ -185,6 +185,190 @@ __global__ __launch_bounds__(CRC_FT) void dmx_crc_fold_kernel(const uint32_t* __
     }
 }
 
+// ---- per-block CRC-32 (DMX_F_BGZF: every member's own check value) ----
+//
+//   dmx_crc_blocks_kernel  the finished CRC-32 of every sw-byte block of the input (the last one
+//                          may be short), one launch.  A workgroup stages one block as the span
+//                          kernel stages a span -- from the 16-byte group that holds the block's
+//                          first byte, zeros in front of the data and behind it up to CRC_S bytes
+//                          -- and runs the same slice-by-16 lookups and lane fold.  What differs
+//                          is the padding, which is no per-launch constant here:
+//                            front   0..15 zero bytes, per block: free (R(0..0 || M) = R(M));
+//                            behind  Z_b = CRC_S - (front + length) zero bytes, per block: divided
+//                                    out with x^-(8 Z_b), the product of two table entries
+//                                    (x^-(8 v) and x^-(8 256 v), Z_b < 2^15), computed by wave 0
+//                                    while the block's loads are in flight;
+//                            a block of more than CRC_S - front bytes (sw near 32 KiB at an
+//                            unaligned address) spills into one more 16-byte group, which thread 0
+//                            runs through one lookup step: R = R(span) x^128 xor R(group), and Z_b
+//                            counts from the end of that group (Z_b < 16).
+//                          The affine term has two values, for a full block and for the short last
+//                          one, computed on the host at launch.  Workgroups stride over the blocks;
+//                          lanes whose slice lies behind the data skip their lookups, so a small sw
+//                          costs loads and lookups for its own bytes only.
+struct CrcUnshift {
+    uint32_t lo[256];   // x^-(8 v)
+    uint32_t hi[128];   // x^-(8 256 v)
+};
+static constexpr CrcUnshift crc_make_unshift() {
+    CrcUnshift U = {};
+    uint32_t x8 = 0xDB710641u;   // x^-1: (P + 1) / x
+    for (int k = 0; k < 3; k++) x8 = crc_cmul(x8, x8);   // x^-8
+    uint32_t p = DMX_CRC_ONE;
+    for (int v = 0; v < 256; v++) { U.lo[v] = p; p = crc_cmul(p, x8); }
+    const uint32_t x2048 = p;    // x^-(8 256)
+    p = DMX_CRC_ONE;
+    for (int v = 0; v < 128; v++) { U.hi[v] = p; p = crc_cmul(p, x2048); }
+    return U;
+}
+static_assert(crc_cmul(0xDB710641u, DMX_CRC_ONE >> 1) == DMX_CRC_ONE, "x^-1 x = 1");
+static_assert(CRC_S <= 128 * 256, "Z_b < 2^15: two table entries");
+__device__ const CrcUnshift g_crc_unshift = crc_make_unshift();
+static constexpr uint32_t crc_x128() {   // x^(8 16): the shift of one 16-byte group
+    uint32_t x = DMX_CRC_ONE >> 1;
+    for (int e = 1; e < 128; e <<= 1) x = crc_cmul(x, x);
+    return x;
+}
+
+// crc_load16 for a block: offsets from the block's aligned base fit 32 bits (g <= CRC_S, lo < 16,
+// hi <= CRC_S + 15), and a word's mask is two shifts: its bytes [a, e) are data
+__device__ __forceinline__ uint4 crc_load16_blk(const uint8_t* __restrict__ base, uint32_t g, uint32_t lo, uint32_t hi) {
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (g + 16 <= lo || g >= hi) return v;   // no byte of the block: nothing is read
+    v = *reinterpret_cast<const uint4*>(base + g);   // 16-byte aligned, shares a byte with the block
+    if (g < lo || g + 16 > hi) {
+        uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (uint32_t i = 0; i < 4; i++) {
+            const int32_t q0 = (int32_t)(g + 4 * i);
+            const int32_t a = min(max((int32_t)lo - q0, 0), 4), e = min(max((int32_t)hi - q0, 0), 4);
+            const uint32_t below_e = (uint32_t)((1ull << (8 * e)) - 1ull), below_a = (uint32_t)((1ull << (8 * a)) - 1ull);
+            w[i] &= below_e & ~below_a;
+        }
+        v = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+    return v;
+}
+
+// one slice-by-16 step: the remainder c extended by the 16 bytes d
+#define CRC_STEP16(c, d, tab)                                                                                          \
+    do {                                                                                                               \
+        const uint32_t x_ = (d).x ^ (c);                                                                               \
+        (c) = tab[15 * 256 + (x_ & 0xFFu)] ^ tab[14 * 256 + ((x_ >> 8) & 0xFFu)] ^ tab[13 * 256 + ((x_ >> 16) & 0xFFu)] ^ \
+              tab[12 * 256 + (x_ >> 24)] ^ tab[11 * 256 + ((d).y & 0xFFu)] ^ tab[10 * 256 + (((d).y >> 8) & 0xFFu)] ^     \
+              tab[9 * 256 + (((d).y >> 16) & 0xFFu)] ^ tab[8 * 256 + ((d).y >> 24)] ^ tab[7 * 256 + ((d).z & 0xFFu)] ^    \
+              tab[6 * 256 + (((d).z >> 8) & 0xFFu)] ^ tab[5 * 256 + (((d).z >> 16) & 0xFFu)] ^ tab[4 * 256 + ((d).z >> 24)] ^ \
+              tab[3 * 256 + ((d).w & 0xFFu)] ^ tab[2 * 256 + (((d).w >> 8) & 0xFFu)] ^                                    \
+              tab[1 * 256 + (((d).w >> 16) & 0xFFu)] ^ tab[0 * 256 + ((d).w >> 24)];                                      \
+    } while (0)
+
+__global__ __launch_bounds__(CRC_T) void dmx_crc_blocks_kernel(const uint8_t* __restrict__ in, uint64_t n, uint32_t sw,
+                                                               uint32_t nblk, uint32_t aff_full, uint32_t aff_tail,
+                                                               uint32_t* __restrict__ crc) {
+    __shared__ __attribute__((aligned(16))) uint32_t tab[CRC_NS * 256];
+    __shared__ __attribute__((aligned(16))) uint32_t stage[CRC_T * CRC_ROW];
+    __shared__ uint32_t wred[CRC_T / 64];
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t i = tid; i < CRC_NS * 256; i += CRC_T) tab[i] = (&g_crc.t[0][0])[i];
+    const uint32_t klane = g_crc.lane[tid];
+    constexpr uint32_t X128 = crc_x128();
+    // block b: its aligned base, the data's bytes [lo, hi) from there
+    auto geom = [&](uint32_t b, const uint8_t*& base, uint32_t& lo, uint32_t& hi) {
+        const uint64_t off = (uint64_t)b * sw;
+        const uint32_t len = (n - off) < sw ? (uint32_t)(n - off) : sw;
+        const uint8_t* p = in + off;
+        lo = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 15);
+        base = p - lo;
+        hi = lo + len;
+    };
+    uint4 v[CRC_Q], vx = make_uint4(0u, 0u, 0u, 0u);   // vx: the group behind the span (thread 0)
+    auto load = [&](uint32_t b) {
+        const uint8_t* base;
+        uint32_t lo, hi;
+        geom(b, base, lo, hi);
+#pragma unroll
+        for (uint32_t i = 0; i < CRC_Q; i++) v[i] = crc_load16_blk(base, 16u * (tid + CRC_T * i), lo, hi);
+        if (tid == 0) vx = crc_load16_blk(base, CRC_S, lo, hi);   // (nothing is read unless hi > CRC_S)
+    };
+    uint32_t b = blockIdx.x;
+    if (b < nblk) load(b);
+    for (; b < nblk; b += gridDim.x) {
+        const uint8_t* base;
+        uint32_t lo, hi;
+        geom(b, base, lo, hi);
+        const bool spill = hi > CRC_S;
+        // x^-(8 Z_b), by wave 0 while the loads fly (thread 0 uses it)
+        uint32_t unshift = 0;
+        if (tid < 64) {
+            const uint32_t Z = (spill ? CRC_S + 16u : (uint32_t)CRC_S) - hi;
+            unshift = dmx_gf2_mulmod(g_crc_unshift.lo[Z & 255u], g_crc_unshift.hi[Z >> 8]);
+        }
+#pragma unroll
+        for (uint32_t i = 0; i < CRC_Q; i++) {
+            const uint32_t q = tid + CRC_T * i, sl = q / (CRC_L / 16);
+            if (sl * CRC_L < hi)   // (a slice behind the data is never read)
+                *reinterpret_cast<uint4*>(&stage[sl * CRC_ROW + 4 * (q % (CRC_L / 16))]) = v[i];
+        }
+        const uint4 gx = vx;
+        __syncthreads();   // (and the tables, the first time)
+        const uint32_t bn = b + gridDim.x;
+        if (bn < nblk) load(bn);   // the next block's loads fly during this one's lookups
+        uint32_t c = 0;
+        if (tid * CRC_L < hi) {
+            const uint4* p = reinterpret_cast<const uint4*>(&stage[tid * CRC_ROW]);
+#pragma unroll
+            for (uint32_t k = 0; k < CRC_L / 16; k++) {
+                const uint4 d = p[k];
+                CRC_STEP16(c, d, tab);
+            }
+        }
+        uint32_t r = dmx_gf2_mulmod(c, klane);
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) r ^= __shfl_xor(r, o);
+        if ((tid & 63) == 0) wred[tid >> 6] = r;
+        __syncthreads();   // (also: every lane has read its slice before the next staging)
+        if (tid == 0) {
+            uint32_t t = 0;
+#pragma unroll
+            for (uint32_t w = 0; w < CRC_T / 64; w++) t ^= wred[w];
+            if (spill) {
+                uint32_t cg = 0;
+                CRC_STEP16(cg, gx, tab);
+                t = dmx_gf2_mulmod(t, X128) ^ cg;
+            }
+            crc[b] = dmx_gf2_mulmod(t, unshift) ^ ((hi - lo) == sw ? aff_full : aff_tail);
+        }
+    }
+}
+
+// the launch of dmx_crc32_blocks_async on stream s (dmx_encode_async shares it: DMX_F_BGZF).  No
+// scratch: every workgroup writes finished values.
+static int dmx_crc32_blocks_launch(dmx_ctx* c, const void* d_in, uint64_t n, uint32_t sw, uint32_t* d_crc,
+                                   hipStream_t s) {
+    const uint64_t nblk64 = (n + sw - 1) / sw;
+    if (nblk64 > 0x7FFFFFFFull) return -(int)E_SZ;
+    if (!nblk64) return 0;
+    const uint32_t nblk = (uint32_t)nblk64;
+    const uint64_t tail = n - (nblk64 - 1) * sw;
+    const uint32_t gmax = 3 * c->ncu;   // 3 workgroups of 52 KiB LDS per CU
+    hipLaunchKernelGGL(dmx_crc_blocks_kernel, dim3(nblk < gmax ? nblk : gmax), dim3(CRC_T), 0, s, (const uint8_t*)d_in,
+                       n, sw, nblk, dmx_crc32_affine(sw), dmx_crc32_affine(tail), d_crc);
+    return 0;
+}
+
+extern "C" int dmx_crc32_blocks_async(dmx_ctx* c, const void* d_in, uint64_t n, int32_t sw, uint32_t* d_crc,
+                                      void* stream) {
+    if (!c || !d_crc || (!d_in && n)) return -(int)E_INVAL;
+    if ((reinterpret_cast<uintptr_t>(d_crc) & 3) != 0) return -(int)E_INVAL;
+    if (sw == 0) sw = DMX_BLK;
+    if (sw < 1 || sw > DMX_BLK) return -(int)E_RANGE;
+    HIPCHK(hipSetDevice(c->device));
+    const int r = dmx_crc32_blocks_launch(c, d_in, n, (uint32_t)sw, d_crc, stream ? (hipStream_t)stream : c->stream);
+    if (r) return r;
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 extern "C" void dmx_crc32_geometry(uint32_t* span, uint32_t* lane_slice) {
     if (span) *span = CRC_S;
     if (lane_slice) *lane_slice = CRC_L;

@@ -40,7 +40,8 @@ struct dmx_ctx {
     dmx_result* res;
     uint32_t* nfb;        // [0] sort fallbacks of the encode in flight (kernels add, K3's scan reads and zeroes), [1] total,
                           // [2] the CRC-32 of a DMX_F_GZIP encode's input (dmx_crc.hip writes, K3's scan reads)
-    uint32_t* crc_rem;    // CRC-32 scratch (dmx_crc.hip): crc_cap span remainders
+    uint32_t* crc_rem;    // CRC-32 scratch (dmx_crc.hip): crc_cap span remainders; under DMX_F_BGZF (which
+                          // ignores DMX_F_GZIP) the encode's finished CRC-32 per block instead, read by K4
     uint64_t crc_cap;     // spans of DMX_BLK bytes it holds: cap_blocks + 2 (0: no workspace yet)
     uint64_t* dbg;        // optional per-block phase stamps (DMX_STAMPS=1)
     uint64_t dbg_cap;

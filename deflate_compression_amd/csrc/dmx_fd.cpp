@@ -542,9 +542,12 @@ extern "C" int dmx_encode_fd_cb(int fd_in, int fd_out, const dmx_opts* opts, uin
 }
 
 // the stream's trailer from the combined check value: Adler-32 big-endian, or (gzip) CRC-32
-// and the byte count mod 2^32, little-endian; returns its length
-static uint64_t stream_trailer(uint8_t* t, bool gz, uint32_t check, uint64_t total) {
-    if (!gz) {
+// and the byte count mod 2^32, little-endian; returns its length.  DMX_F_BGZF has none: every
+// member carries its own, the chunks' members concatenate as they are, and the device appends
+// the end-of-file member to the last chunk (DMX_F_FINAL).
+static uint64_t stream_trailer(uint8_t* t, uint32_t pflags, uint32_t check, uint64_t total) {
+    if (pflags & DMX_F_BGZF) return 0;
+    if (!(pflags & DMX_F_GZIP)) {
         for (int k = 0; k < 4; k++) t[k] = (uint8_t)(check >> (24 - 8 * k));
         return 4;
     }
@@ -562,7 +565,7 @@ static int encode_fd_on(int device, int fd_in, int fd_out, const dmx_opts* opts,
     if (chunk < sw) chunk = sw;
     chunk -= chunk % sw;
     const uint32_t pflags = o.flags & (DMX_F_LAZY | DMX_F_SPLIT | DMX_F_DICT | DMX_F_EXACT_SORT | DMX_F_STORE_CHECK |
-                                       DMX_F_DEEP | DMX_F_GZIP);
+                                       DMX_F_DEEP | DMX_F_GZIP | DMX_F_BGZF);
     const bool gz = (pflags & DMX_F_GZIP) != 0;   // one gzip member: CRC-32 where zlib has Adler-32
     FdReader R = {fd_in, false, 0, 0, -1, true};
     {   // a regular file of known size from the current offset: parallel preads
@@ -708,7 +711,7 @@ static int encode_fd_on(int device, int fd_in, int fd_out, const dmx_opts* opts,
     if (!r) r = S.err;
     if (!r && fd_out >= 0) {
         uint8_t tail[8];
-        r = write_full(fd_out, tail, stream_trailer(tail, gz, adler, nin_total));
+        r = write_full(fd_out, tail, stream_trailer(tail, pflags, adler, nin_total));
     }
     if (R.seekable) (void)lseek(fd_in, (off_t)R.off, SEEK_SET);   // consumed, as read() would leave it
     // nothing may still run on the cached buffers when the lock is released
@@ -719,7 +722,7 @@ static int encode_fd_on(int device, int fd_in, int fd_out, const dmx_opts* opts,
         pthread_mutex_lock(&g_fd_last_mu);
         g_fd_last.chunks = nchunks;
         g_fd_last.bytes_in = nin_total;
-        g_fd_last.bytes_out = nout_total + (gz ? 8 : 4);
+        g_fd_last.bytes_out = nout_total + ((pflags & DMX_F_BGZF) ? 0 : gz ? 8 : 4);
         g_fd_last.wall_ms = fd_now_ms() - t_begin;
         g_fd_last.read_ms = S.read_ms;
         g_fd_last.h2d_ms = h2d_ms;
@@ -917,7 +920,7 @@ extern "C" int dmx_encode_fd_multi(int fd_in, int fd_out, const dmx_opts* opts, 
     if (J.nchunks == 0) J.nchunks = 1;   // an empty input is one empty chunk (header, EOB block, trailer)
     J.o = o;
     J.pflags = o.flags & (DMX_F_LAZY | DMX_F_SPLIT | DMX_F_DICT | DMX_F_EXACT_SORT | DMX_F_STORE_CHECK | DMX_F_DEEP |
-                          DMX_F_GZIP);
+                          DMX_F_GZIP | DMX_F_BGZF);
     J.ndev = ndev < (int)J.nchunks ? ndev : (int)J.nchunks;
     pthread_mutex_init(&J.mu, NULL);
     pthread_cond_init(&J.cv, NULL);
@@ -950,7 +953,7 @@ extern "C" int dmx_encode_fd_multi(int fd_in, int fd_out, const dmx_opts* opts, 
     if (!r) r = J.err;
     if (!r && fd_out >= 0) {
         uint8_t tail[8];
-        r = write_full(fd_out, tail, stream_trailer(tail, (J.pflags & DMX_F_GZIP) != 0, J.adler, J.size - J.off0));
+        r = write_full(fd_out, tail, stream_trailer(tail, J.pflags, J.adler, J.size - J.off0));
     }
     if (!r) (void)lseek(fd_in, (off_t)J.size, SEEK_SET);   // consumed, as read() would leave it
     for (int w = 0; w < J.ndev; w++)   // an error may have left copies in flight from the cached buffers

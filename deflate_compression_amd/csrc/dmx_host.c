@@ -180,20 +180,25 @@ int deflate_compress(int fd_in, int fd_out, int fd_stats, swi sw, int ops) {
         exact = mode && strcmp(mode, "exact") == 0;
     }
     /* DMX_FORMAT: the container -- unset / "zlib" the zlib stream, "gzip" one gzip member
-     * (DMX_F_GZIP); anything else fails before anything is read or written */
+     * (DMX_F_GZIP), "bgzf" a gzip member per sw block and the end-of-file member (DMX_F_BGZF);
+     * anything else fails before anything is read or written */
     const char* fm = getenv("DMX_FORMAT");
-    if (fm && *fm && strcmp(fm, "zlib") != 0 && strcmp(fm, "gzip") != 0) return -E_INVAL;
+    if (fm && *fm && strcmp(fm, "zlib") != 0 && strcmp(fm, "gzip") != 0 && strcmp(fm, "bgzf") != 0) return -E_INVAL;
+    const int bgzf = fm && strcmp(fm, "bgzf") == 0;
     const char* mc = getenv("DMX_MAX_CHAIN");
     dmx_opts o;
     o.sw = swv;
     o.max_chain = mc ? atoi(mc) : 0;
-    o.flags = (fm && strcmp(fm, "gzip") == 0) ? DMX_GZIP : DMX_ZLIB;
+    o.flags = bgzf ? DMX_BGZF : (fm && strcmp(fm, "gzip") == 0) ? DMX_GZIP : DMX_ZLIB;
     const char* lz = getenv("DMX_LAZY");   /* 1 = lazy evaluation (DMX_F_LAZY); default greedy */
     if (lz && atoi(lz) > 0) o.flags |= DMX_F_LAZY;
     const char* sp = getenv("DMX_SPLIT");  /* 1 = adaptive block splitting (DMX_F_SPLIT) */
     if (sp && atoi(sp) > 0) o.flags |= DMX_F_SPLIT;
     const char* dc = getenv("DMX_DICT");   /* 1 = cross-block dictionary (DMX_F_DICT) */
     if (dc && atoi(dc) > 0) o.flags |= DMX_F_DICT;
+    /* BGZF members are independent and hold one DEFLATE block: neither option goes with it, and
+     * nothing is read or written */
+    if (bgzf && (o.flags & (DMX_F_SPLIT | DMX_F_DICT))) return -E_INVAL;
     const char* sc = getenv("DMX_STORE_CHECK");   /* 1 = noise blocks stored unparsed (§4.7);
                                                    * not with fd_stats: such blocks have no tokens */
     if (sc && atoi(sc) > 0 && fd_stats < 0) o.flags |= DMX_F_STORE_CHECK;

@@ -23,6 +23,7 @@
 
 #include "../../include/dmx.h"
 #include "dmx_crc.h"
+#include "dmx_internal.h"
 
 #define MAXBITS 15
 #define FAST 9
@@ -378,4 +379,67 @@ int deflate_decompress(struct string_len* decompr_dat, struct string_len* compr_
     decompr_dat->str = s.out;
     decompr_dat->len = s.olen;
     return 0;
+}
+
+/* The block index of a BGZF file (SAM/BAM specification §4.1; include/dmx.h): a series of gzip
+ * members with FEXTRA set, each carrying its own size - 1 as BSIZE in the "BC" subfield
+ * (SI1 'B', SI2 'C', SLEN 2), so the walk reads headers and trailers only.  The DEFLATE data
+ * of a member starts behind its header (gzip_header: FNAME / FCOMMENT / FHCRC are skipped if a
+ * writer set them) and its trailer is the member's last 8 bytes. */
+int dmx_bgzf_index(const uint8_t* z, uint64_t zlen, dmx_iblock* idx, uint32_t* crc, uint32_t cap, uint32_t* nblk,
+                   uint64_t* out_len) {
+    if ((!z && zlen) || !nblk || (!idx && cap)) return -(int)E_INVAL;
+    uint64_t p = 0, total = 0, cnt = 0;
+    *nblk = 0;
+    if (out_len) *out_len = 0;
+    while (p < zlen) {
+        const uint8_t* m = z + p;
+        const uint64_t left = zlen - p;
+        if (left < 12) {   /* the fixed header and XLEN: is what is there a gzip / deflate / FEXTRA member at all? */
+            if (m[0] != 0x1F || (left > 1 && m[1] != 0x8B) || (left > 2 && m[2] != 8) || (left > 3 && !(m[3] & 4)))
+                return -(int)E_ZHEAD;
+            return -(int)E_LEN;
+        }
+        if (m[0] != 0x1F || m[1] != 0x8B || m[2] != 8 || !(m[3] & 4) || (m[3] & 0xE0)) return -(int)E_ZHEAD;
+        const uint64_t xlen = (uint64_t)m[10] | ((uint64_t)m[11] << 8);
+        if (left < 12 + xlen) return -(int)E_LEN;
+        uint64_t bsize = 0;
+        int found = 0;
+        for (uint64_t q = 12; q + 4 <= 12 + xlen;) {   /* the subfields: SI1 SI2 SLEN(2) data */
+            const uint64_t slen = (uint64_t)m[q + 2] | ((uint64_t)m[q + 3] << 8);
+            if (q + 4 + slen > 12 + xlen) break;   /* a subfield past XLEN: no BC found in a sound one */
+            if (m[q] == 'B' && m[q + 1] == 'C' && slen == 2) {
+                bsize = ((uint64_t)m[q + 4] | ((uint64_t)m[q + 5] << 8)) + 1;
+                found = 1;
+                break;
+            }
+            q += 4 + slen;
+        }
+        if (!found) return -(int)E_ZHEAD;
+        if (left < bsize) return -(int)E_LEN;
+        size_t body = 0;
+        const long e = gzip_header(m, (size_t)bsize, &body);   /* (the member alone: nothing behind it is read) */
+        if (e) return -(int)E_ZHEAD;
+        if ((uint64_t)body + 8 > bsize) return -(int)E_ZHEAD;   /* BSIZE leaves no room for the trailer */
+        const uint8_t* t = m + bsize - 8;
+        const uint32_t mcrc = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
+        const uint32_t isize = (uint32_t)t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
+        if (isize > DMX_BLK) return -(int)E_RANGE;
+        if (isize) {
+            if (cnt < cap) {
+                idx[cnt].bit = 8 * (p + (uint64_t)body);
+                idx[cnt].out_off = total;
+                idx[cnt].out_len = isize;
+                idx[cnt].reserved = 0;
+                if (crc) crc[cnt] = mcrc;
+            }
+            cnt++;
+            if (cnt > 0xFFFFFFFFull) return -(int)E_RANGE;
+            total += isize;
+        }
+        p += bsize;
+    }
+    *nblk = (uint32_t)cnt;
+    if (out_len) *out_len = total;
+    return cnt > cap ? -(int)E_SZ : 0;
 }

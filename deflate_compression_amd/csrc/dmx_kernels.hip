@@ -2627,7 +2627,10 @@ __device__ __forceinline__ uint32_t store_check_block(const uint8_t* __restrict_
         const bool sto = 256 * S2 <= m2 + (m2 >> 4) + 256 * m && 16 * Q >= (uint64_t)bn && 64 * coll <= 4 * Q;
 #endif
         // the speculative copy (above) when the whole block fits the output at that offset
-        const bool spec = sto && (spec_stored_bit(b, sw, flags) >> 3) + (uint64_t)bn + 16 <= out_cap;
+        // (not under DMX_F_BGZF: its stored blocks lie sw + 31 bytes apart, every one behind a header
+        // of its own; they are then prestored 1, the whole-copy prefix is empty, and K4 copies them)
+        const bool spec = sto && !(flags & DMX_F_BGZF) &&
+                          (spec_stored_bit(b, sw, flags) >> 3) + (uint64_t)bn + 16 <= out_cap;
         info[b].prestored = sto ? (spec ? 3u : 1u) : 0u;
         pass_s = spec ? 1u : 0u;
 #ifdef DMX_K0_NOCOPY
@@ -3000,7 +3003,12 @@ __global__ __launch_bounds__(256) void dmx_fill_kernel(const uint8_t* __restrict
         const uint32_t b = b0 + i;
         if (b >= nblk || !(wl_codes(wl, cap)[b] & 8u)) continue;
         const uint32_t r = wl_dup(wl, cap)[b];
-        const uint64_t Ob = info[b].off_bits, Or = info[r].off_bits, Lb = info[b].len_bits;
+        uint64_t Ob = info[b].off_bits, Or = info[r].off_bits, Lb = info[b].len_bits;
+        if (flags & DMX_F_BGZF) {   // the whole member: same bytes, hence same BSIZE, CRC-32 and byte count
+            Ob -= 144;
+            Or -= 144;
+            Lb = 144 + ((Lb + 7) & ~7ull) + 64;
+        }
         const uint64_t gw0 = Ob >> 5;
         const uint32_t nwords = (uint32_t)(((Ob & 31) + Lb + 31) >> 5);
         for (uint32_t k = lane; k < nwords; k += 64) {
@@ -4280,7 +4288,8 @@ __device__ __forceinline__ void huff_one(const uint32_t b, const uint32_t* __res
     const uint32_t* hg = hist_g + (uint64_t)b * DMX_HIST;
     if (info[b].prestored & 1u) return;   // K0 wrote the stored record (1, 3)
     const uint32_t bn = info[b].n;
-    const uint32_t final_bit = ((flags & DMX_F_FINAL) && b == nblk - 1) ? 1u : 0u;
+    // (DMX_F_BGZF: every block ends a member of its own)
+    const uint32_t final_bit = (((flags & DMX_F_FINAL) && b == nblk - 1) || (flags & DMX_F_BGZF)) ? 1u : 0u;
 
     [[maybe_unused]] uint64_t kt0 = K2T();
     for (int s = (int)lane; s < 288; s += 64) S.fll[s] = s < 286 ? (s == 256 ? 1u : hg[s]) : 0u;   // + end of block
@@ -4600,11 +4609,66 @@ __device__ __forceinline__ void put_header(uint32_t* out32, uint32_t flags) {
     }
 }
 
+// DMX_F_BGZF (dmx.h): block b is a gzip member of its own -- 18 header bytes, its DEFLATE data
+// from a byte boundary, zero bits to the next one, CRC-32 and byte count -- so in the scan its
+// layout element is the plain {s = 0, a = 0, c = member bits} (every member starts byte-aligned
+// and has a whole-byte length); off_bits points BGZF_HDR bits into the member, at the data, and
+// len_bits is the data's length, as in the other containers, so the pack kernel's block paths
+// run unchanged.  A member's edge words are shared with its neighbours, and the data's edge words
+// with the member's own header and trailer: the apply launch zeroes every word the header and
+// the trailer touch (bgzf_zero_edges), and the pack kernel ORs both in (bgzf_member_framing).
+#define BGZF_HDR 144u   // header bits
+#define BGZF_TRL 64u    // trailer bits
+#define BGZF_EOF 224u   // the end-of-file member's bits
+__device__ __forceinline__ uint64_t bgzf_data_bits(const dmx_blkinfo& bi) {
+    // a stored block at a byte boundary: 3 bits, 5 of padding, LEN / NLEN, the bytes
+    return bi.btype == 0 ? 40 + 8 * (uint64_t)bi.n : (uint64_t)bi.hdr_bits + bi.body_bits;
+}
+// the end-of-file member at bit T (a byte boundary; its words are zeroed):
+// 1F 8B 08 04 00 00 00 00 00 FF 06 00 42 43 02 00 1B 00 03 00 00 00 00 00 00 00 00 00
+__device__ __forceinline__ void bgzf_put_eof(uint32_t* out32, uint64_t T) {
+    gor_bits(out32, T, 0x04088B1Fu, 32);
+    gor_bits(out32, T + 64, 0x0006FF00u, 32);
+    gor_bits(out32, T + 96, 0x00024342u, 32);
+    gor_bits(out32, T + 128, 0x0003001Bu, 32);
+}
+// the header and trailer of the member whose data is the dl bits at O: BSIZE = member bytes - 1,
+// crc / isize = the block's CRC-32 and byte count
+__device__ __forceinline__ void bgzf_member_framing(uint32_t* out32, uint64_t O, uint64_t dl, uint32_t crc,
+                                                    uint32_t isize) {
+    const uint64_t m = O - BGZF_HDR, e = align8(O + dl);
+    gor_bits(out32, m, 0x04088B1Fu, 32);
+    gor_bits(out32, m + 64, 0x0006FF00u, 32);
+    gor_bits(out32, m + 96, 0x00024342u, 32);
+    gor_bits(out32, m + 128, (uint32_t)((e + BGZF_TRL - m) / 8 - 1), 16);
+    gor_bits(out32, e, crc, 32);
+    gor_bits(out32, e + 32, isize, 32);
+}
+// zero the words that the header and the trailer of the member [m, m + l) touch (dl data bits)
+__device__ __forceinline__ void bgzf_zero_edges(uint32_t* out32, uint64_t m, uint64_t l, uint64_t dl) {
+    for (uint64_t w = m >> 5; w <= (m + BGZF_HDR - 1) >> 5; w++) out32[w] = 0;
+    for (uint64_t w = (m + BGZF_HDR + dl - 1) >> 5; w <= (m + l - 1) >> 5; w++) out32[w] = 0;
+}
+// the framing behind the last block: where the DEFLATE data (BGZF: the last member) ends for T =
+// the end of the last block, and the bits that follow (trailer; BGZF: the end-of-file member)
+__device__ __forceinline__ uint64_t stream_end(uint32_t flags, uint32_t nblk, uint64_t T) {
+    if (flags & DMX_F_BGZF) return T;
+    return (flags & DMX_F_FINAL) ? align8(T) : (nblk == 0 ? align8(T) : align8(T + 3) + 32);
+}
+__device__ __forceinline__ uint32_t tail_bits(uint32_t flags) {
+    if (flags & DMX_F_BGZF) return (flags & DMX_F_FINAL) ? BGZF_EOF : 0u;
+    return trl_bits(flags);
+}
+
 // the header, the sync flush after a non-final shard's last block, the trailer (big-endian
 // Adler-32, or with DMX_F_GZIP little-endian CRC-32 and input length n mod 2^32; `adler` is
 // the stream's check value, either one); T = end of the last block, end = byte-aligned end of the DEFLATE data.
 __device__ __forceinline__ void stream_framing(uint32_t* out32, uint32_t flags, uint32_t nblk, uint64_t T,
                                                uint64_t end, uint32_t adler, uint64_t n) {
+    if (flags & DMX_F_BGZF) {   // (T == end: behind the last member, or 0)
+        if (flags & DMX_F_FINAL) bgzf_put_eof(out32, end);
+        return;
+    }
     const uint64_t start = hdr_bits(flags);
     put_header(out32, flags);
     if (nblk == 0 && (flags & DMX_F_FINAL)) gor_bits(out32, start, 3u, 3);  // BFINAL=1, BTYPE=01, EOB=0000000
@@ -4644,15 +4708,17 @@ struct ScanTile {
     uint64_t pad_[4];
 };
 
-__device__ __forceinline__ Mono blk_elem(const dmx_blkinfo& bi) {
+__device__ __forceinline__ Mono blk_elem(const dmx_blkinfo& bi, uint32_t flags) {
     Mono e = {0, 0, 0};
-    if (bi.btype == 0) { e.s = 1; e.a = 3; e.c = 32 + 8 * (uint64_t)bi.n; }
+    if (flags & DMX_F_BGZF) e.c = BGZF_HDR + align8(bgzf_data_bits(bi)) + BGZF_TRL;   // a whole member
+    else if (bi.btype == 0) { e.s = 1; e.a = 3; e.c = 32 + 8 * (uint64_t)bi.n; }
     else { e.c = bi.hdr_bits + bi.body_bits; }
     return e;
 }
 
 __global__ __launch_bounds__(SCAN_TILE) void dmx_scan_tile_kernel(dmx_blkinfo* __restrict__ info, uint32_t nblk,
-                                                                 uint64_t n, uint32_t sw, ScanTile* __restrict__ tiles,
+                                                                 uint64_t n, uint32_t sw, uint32_t flags,
+                                                                 ScanTile* __restrict__ tiles,
                                                                  const uint16_t* __restrict__ codes,
                                                                  const uint32_t* __restrict__ dup,
                                                                  dmx_subinfo* __restrict__ sub_g) {
@@ -4682,7 +4748,7 @@ __global__ __launch_bounds__(SCAN_TILE) void dmx_scan_tile_kernel(dmx_blkinfo* _
             info[b].nsub = ri.nsub;
             sub_g[(uint64_t)b * DMX_NSUB] = sub_g[(uint64_t)r * DMX_NSUB];
         }
-        e = blk_elem(bi);
+        e = blk_elem(bi, flags);
         const uint64_t end_b = (uint64_t)b * sw + bi.n;
         s1 = bi.adl_s % ADL_MOD;
         s2 = (bi.adl_w % ADL_MOD + ((n - end_b) % ADL_MOD) * s1) % ADL_MOD;
@@ -4811,11 +4877,12 @@ __global__ __launch_bounds__(ST) void dmx_scan_kernel(ScanTile* __restrict__ til
         s1 = (1 + s1) % ADL_MOD;
         s2 = (n % ADL_MOD + s2) % ADL_MOD;
         // the stream's check value: Adler-32, or the CRC-32 the CRC launches left (DMX_F_GZIP)
-        const uint32_t adler = crc ? crc[0] : (uint32_t)((s2 << 16) | s1);
+        // (DMX_F_BGZF has no stream-wide one: 0)
+        const uint32_t adler = (flags & DMX_F_BGZF) ? 0u : crc ? crc[0] : (uint32_t)((s2 << 16) | s1);
         uint64_t T = mapply(carry_s, start);
-        if (nblk == 0 && (flags & DMX_F_FINAL)) T = start + 10;   // empty input: fixed block, EOB only
-        uint64_t end = (flags & DMX_F_FINAL) ? align8(T) : (nblk == 0 ? align8(T) : align8(T + 3) + 32);
-        uint64_t out_len = end / 8 + trl_bits(flags) / 8;
+        if (nblk == 0 && (flags & DMX_F_FINAL) && !(flags & DMX_F_BGZF)) T = start + 10;   // empty input: fixed block, EOB only
+        uint64_t end = stream_end(flags, nblk, T);
+        uint64_t out_len = end / 8 + tail_bits(flags) / 8;
         int32_t status = 0;
         if (((out_len + 3) & ~3ull) > out_cap) status = -(int32_t)E_SZ;
         res->out_len = out_len;
@@ -4848,7 +4915,7 @@ __global__ __launch_bounds__(ST) void dmx_scan_kernel(ScanTile* __restrict__ til
     if (s_status) return;
     // zero the words past the last block (the framing goes there)
     const uint64_t T = s_T, end = s_end;
-    const uint64_t tail_end = end + trl_bits(flags);
+    const uint64_t tail_end = end + tail_bits(flags);
     // (word T >> 5, when the last block ends inside it, is that block's last word: the apply
     // launch zeroes it, keeping any bytes of the whole-copy prefix it holds)
     const uint64_t tw0 = nblk ? (T + 31) >> 5 : T >> 5;
@@ -4877,7 +4944,15 @@ __global__ __launch_bounds__(SCAN_TILE) void dmx_scan_apply_kernel(dmx_blkinfo* 
     lp.c = bi.off_bits; lp.s = (uint32_t)(bi.len_bits >> 32); lp.a = bi.len_bits & 0xFFFFFFFFu;
     const Mono pre = mcompose(tp, lp);
     const uint64_t o = mapply(pre, start);
-    const uint64_t l = mapply(blk_elem(bi), o) - o;
+    const uint64_t l = mapply(blk_elem(bi, flags), o) - o;
+    if (flags & DMX_F_BGZF) {   // o, l: the member; the block record points at its data
+        const uint64_t dl = bgzf_data_bits(bi);
+        info[b].off_bits = o + BGZF_HDR;
+        info[b].len_bits = dl;
+        bgzf_zero_edges(out32, o, l, dl);   // (no whole-copy prefix under the flag: plain zeroing)
+        if (wl && !is_dup(codes, b)) L4[atomicAdd(&wl[WL_N4], 1u)] = b;
+        return;
+    }
     info[b].off_bits = o;
     info[b].len_bits = l;
     if (!wl) {
@@ -4969,8 +5044,8 @@ __global__ __launch_bounds__(SCAN_TILE) void dmx_scan_apply1_kernel(dmx_blkinfo*
     if (mine) s_pre = mcompose(lane ? mcompose(wpre, before) : wpre, part);
     // the stream's end and status (every workgroup: nothing is written past out_cap)
     const uint64_t T = mapply(tot, start);
-    const uint64_t end = (flags & DMX_F_FINAL) ? align8(T) : align8(T + 3) + 32;
-    const uint64_t out_len = end / 8 + trl_bits(flags) / 8;
+    const uint64_t end = stream_end(flags, nblk, T);
+    const uint64_t out_len = end / 8 + tail_bits(flags) / 8;
     const int32_t status = (((out_len + 3) & ~3ull) > out_cap) ? -(int32_t)E_SZ : 0;
     if (lastwg && tid == 0) {
         uint64_t a1 = 0, a2 = 0, ntk = 0, nst = 0, nfx = 0, q0 = 0, q2 = 0, q3 = 0, qu = 0;
@@ -4984,7 +5059,7 @@ __global__ __launch_bounds__(SCAN_TILE) void dmx_scan_apply1_kernel(dmx_blkinfo*
         res->end_bits = T;
         res->n = n;
         res->ntokens = ntk;
-        res->adler = crc ? crc[0] : (uint32_t)((a2 << 16) | a1);   // (as dmx_scan_kernel)
+        res->adler = (flags & DMX_F_BGZF) ? 0u : crc ? crc[0] : (uint32_t)((a2 << 16) | a1);   // (as dmx_scan_kernel)
         res->status = status;
         res->nblocks = nblk;
         res->nstored = (uint32_t)nst;
@@ -5004,7 +5079,7 @@ __global__ __launch_bounds__(SCAN_TILE) void dmx_scan_apply1_kernel(dmx_blkinfo*
     }
     if (status) return;
     if (lastwg) {   // zero the words past the last block (the framing goes there)
-        const uint64_t tail_end = end + trl_bits(flags);
+        const uint64_t tail_end = end + tail_bits(flags);
         for (uint64_t w = ((T + 31) >> 5) + tid; w < ((tail_end + 31) >> 5); w += SCAN_TILE) out32[w] = 0;   // (as dmx_scan_kernel)
     }
     __syncthreads();   // (s_pre)
@@ -5016,7 +5091,15 @@ __global__ __launch_bounds__(SCAN_TILE) void dmx_scan_apply1_kernel(dmx_blkinfo*
     lp.c = bi.off_bits; lp.s = (uint32_t)(bi.len_bits >> 32); lp.a = bi.len_bits & 0xFFFFFFFFu;
     const Mono pre = mcompose(tp, lp);
     const uint64_t o = mapply(pre, start);
-    const uint64_t l = mapply(blk_elem(bi), o) - o;
+    const uint64_t l = mapply(blk_elem(bi, flags), o) - o;
+    if (flags & DMX_F_BGZF) {   // (as dmx_scan_apply_kernel)
+        const uint64_t dl = bgzf_data_bits(bi);
+        info[b].off_bits = o + BGZF_HDR;
+        info[b].len_bits = dl;
+        bgzf_zero_edges(out32, o, l, dl);
+        if (wl && !is_dup(codes, b)) L4[atomicAdd(&wl[WL_N4], 1u)] = b;
+        return;
+    }
     info[b].off_bits = o;
     info[b].len_bits = l;
     if (!wl) {
@@ -5072,8 +5155,7 @@ __device__ __forceinline__ void pack_framing(uint32_t* out32, uint32_t flags, ui
     if (b == 0) put_header(out32, flags);
     if (b == nblk - 1) {
         const uint64_t T = res->end_bits;
-        const uint64_t end = (flags & DMX_F_FINAL) ? align8(T) : align8(T + 3) + 32;
-        stream_framing(out32, flags & ~DMX_F_HEADER, nblk, T, end, res->adler, res->n);
+        stream_framing(out32, flags & ~DMX_F_HEADER, nblk, T, stream_end(flags, nblk, T), res->adler, res->n);
     }
 }
 
@@ -5082,7 +5164,7 @@ __device__ __forceinline__ void pack_one(const uint32_t b, const uint8_t* __rest
                                          const uint32_t* __restrict__ hdr_g, const dmx_blkinfo* __restrict__ info,
                                          const dmx_subinfo* __restrict__ sub_g,
                                          uint32_t nblk, uint32_t flags, uint32_t* __restrict__ out32,
-                                         dmx_result* __restrict__ res) {
+                                         dmx_result* __restrict__ res, const uint32_t* __restrict__ bcrc) {
     __shared__ uint32_t stage[PK_RING];
     __shared__ uint32_t code[DMX_HIST];
 #ifndef DMX_PACK_OLD
@@ -5098,7 +5180,10 @@ __device__ __forceinline__ void pack_one(const uint32_t b, const uint8_t* __rest
     const uint64_t O = bi.off_bits, Lb = bi.len_bits;
     const uint32_t s0 = (uint32_t)(O & 31);
     const uint32_t nwords = (uint32_t)((s0 + Lb + 31) >> 5);
-    const uint32_t final_bit = ((flags & DMX_F_FINAL) && b == nblk - 1) ? 1u : 0u;
+    const uint32_t final_bit = (((flags & DMX_F_FINAL) && b == nblk - 1) || (flags & DMX_F_BGZF)) ? 1u : 0u;
+    // DMX_F_BGZF: the member's header and trailer around the data (bcrc: the blocks' CRC-32s).  The
+    // data's first and last words are then shared with those, not with a neighbour: same atomicOr.
+    if (tid == 0 && (flags & DMX_F_BGZF)) bgzf_member_framing(out32, O, Lb, bcrc[b], bi.n);
     if (bi.btype == 0) {
         // stored block straight from the input to the output, no LDS: the 3 header bits at s0,
         // LEN/NLEN at byte P/8, the data from byte B0 (bit offsets relative to word O >> 5).
@@ -5358,11 +5443,12 @@ __global__ __launch_bounds__(PT) void dmx_pack_kernel(const uint8_t* __restrict_
                                                       uint32_t nblk, uint32_t flags, uint32_t* __restrict__ out32,
                                                       dmx_result* __restrict__ res,
                                                       const uint32_t* __restrict__ wl, const uint32_t* __restrict__ L4,
-                                                      const uint16_t* __restrict__ codes) {
+                                                      const uint16_t* __restrict__ codes,
+                                                      const uint32_t* __restrict__ bcrc) {
     if (!L4) {   // a workgroup per block; with work lists, the whole-copy prefix returns at once
         if (wl && wl_skip(blockIdx.x, wl[WL_M], nblk)) return;
         if (is_dup(codes, blockIdx.x)) return;   // dmx_dup_copy_kernel's
-        pack_one(blockIdx.x, in, sw, tok_g, codes_g, hdr_g, info, sub_g, nblk, flags, out32, res);
+        pack_one(blockIdx.x, in, sw, tok_g, codes_g, hdr_g, info, sub_g, nblk, flags, out32, res, bcrc);
         if (wl && blockIdx.x == 0 && threadIdx.x == 0) wl_hint_put(wl, 3, wl[WL_N4]);
         return;
     }
@@ -5370,7 +5456,7 @@ __global__ __launch_bounds__(PT) void dmx_pack_kernel(const uint8_t* __restrict_
     if (blockIdx.x == 0 && threadIdx.x == 0) wl_hint_put(wl, 3, cnt);
     for (uint32_t i = blockIdx.x; i < cnt; i += gridDim.x) {
         __syncthreads();   // the previous block's LDS reads are done
-        pack_one(L4[i], in, sw, tok_g, codes_g, hdr_g, info, sub_g, nblk, flags, out32, res);
+        pack_one(L4[i], in, sw, tok_g, codes_g, hdr_g, info, sub_g, nblk, flags, out32, res, bcrc);
     }
 }
 
@@ -5446,7 +5532,13 @@ extern "C" uint64_t dmx_max_compressed(uint64_t n, int32_t sw) {
     return ((n + 5 * nblk + 2 + 4 + 5 + 16) + 3) & ~3ull;
 }
 // the same for a container: DMX_F_GZIP frames with 18 bytes (10 + 8) where zlib has 6 (2 + 4)
+// DMX_F_BGZF: 26 bytes (18 + 8) around every block and the 28-byte end-of-file member
 extern "C" uint64_t dmx_max_compressed_flags(uint64_t n, int32_t sw, uint32_t flags) {
+    if (flags & DMX_F_BGZF) {
+        if (sw <= 0 || sw > DMX_BLK) sw = DMX_BLK;
+        const uint64_t nblk = (n + (uint64_t)sw - 1) / (uint64_t)sw;
+        return dmx_max_compressed(n, sw) + 26 * nblk + 28;
+    }
     return dmx_max_compressed(n, sw) + ((flags & DMX_F_GZIP) ? 12u : 0u);
 }
 
@@ -5702,6 +5794,13 @@ extern "C" int dmx_encode_async(dmx_ctx* c, const void* d_in, uint64_t n, void* 
     if (o.max_chain < 0) return -(int)E_RANGE;
     if (o.deep_chain < 0 || o.deep_chain > 255) return -(int)E_RANGE;
     if ((reinterpret_cast<uintptr_t>(d_out) & 3) != 0) return -(int)E_INVAL;
+    // DMX_F_BGZF: members are independent (no DMX_F_DICT) and hold one DEFLATE block (no DMX_F_SPLIT
+    // so far); every member frames itself, so the stream's own header / trailer flags are dropped here
+    // and the kernels see hdr_bits() == trl_bits() == 0
+    if (o.flags & DMX_F_BGZF) {
+        if (o.flags & (DMX_F_DICT | DMX_F_SPLIT)) return -(int)E_INVAL;
+        o.flags &= ~(DMX_F_HEADER | DMX_F_TRAILER | DMX_F_GZIP);
+    }
     uint32_t dict_len = 0;   // DMX_F_DICT: history of block 0 (the last sw bytes are used)
     if ((o.flags & DMX_F_DICT) && o.dict && o.dict_len) {
         dict_len = o.dict_len < (uint64_t)o.sw ? (uint32_t)o.dict_len : (uint32_t)o.sw;
@@ -5813,10 +5912,17 @@ extern "C" int dmx_encode_async(dmx_ctx* c, const void* d_in, uint64_t n, void* 
         crcw = c->nfb + 2;
         dmx_crc32_launch(c, d_in, n, c->nfb + 2, s);   // (its capacity was checked above)
     }
+    // DMX_F_BGZF: every member's CRC-32, one launch into the CRC scratch (a word per block:
+    // nblk <= cap_blocks < crc_cap), which K4 reads
+    const uint32_t* bcrc = NULL;
+    if ((o.flags & DMX_F_BGZF) && nblk) {
+        bcrc = c->crc_rem;
+        dmx_crc32_blocks_launch(c, d_in, n, (uint32_t)o.sw, c->crc_rem, s);
+    }
     const uint32_t ntile = (nblk + SCAN_TILE - 1) / SCAN_TILE;
     if (nblk)
         hipLaunchKernelGGL(dmx_scan_tile_kernel, dim3(ntile), dim3(SCAN_TILE), 0, s, c->info, nblk, n, (uint32_t)o.sw,
-                           c->tiles, dupk, dupa, c->sub);
+                           o.flags, c->tiles, dupk, dupa, c->sub);
     uint32_t* L4 = wl ? wl + WL_HDR + 2 * c->cap_blocks : NULL;
     uint32_t* hintp = (!wl && (o.flags & DMX_F_STORE_CHECK)) ? c->whint_dev : NULL;
     if (nblk && ntile <= SA1_MAXT && !c->hk_scan3) {   // (hk_scan3: the three-launch scan at any size, tests)
@@ -5833,7 +5939,7 @@ extern "C" int dmx_encode_async(dmx_ctx* c, const void* d_in, uint64_t n, void* 
     if (nblk)
         hipLaunchKernelGGL(dmx_pack_kernel, dim3(wl && wsh.list4 ? list_grid(nblk, wsh.n4, 2 * c->ncu, 16 * c->ncu) : nblk),
                            dim3(PT), 0, s, (const uint8_t*)d_in, (uint32_t)o.sw, c->tok, c->codes, c->hdr, c->info, c->sub,
-                           nblk, o.flags, (uint32_t*)d_out, c->res, wl, wl && wsh.list4 ? L4 : NULL, dupk);
+                           nblk, o.flags, (uint32_t*)d_out, c->res, wl, wl && wsh.list4 ? L4 : NULL, dupk, bcrc);
     // the blocks K4 skipped that K0 did not complete: dups, and the stored prefix unless every
     // block is a full 16-byte aligned one (a wave per 4 blocks)
 #ifdef DMX_K0_NOREST

@@ -18,7 +18,7 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
-from . import DMX_F_FINAL, DMX_F_HEADER, adler32_combine, crc32_combine
+from . import DMX_F_BGZF, DMX_F_FINAL, DMX_F_HEADER, adler32_combine, crc32_combine
 
 BLOCK = 32768
 
@@ -33,6 +33,13 @@ def shard_range(n: int, rank: int, world: int, sw: int = BLOCK) -> tuple[int, in
 
 def shard_flags(rank: int, world: int) -> int:
     return (DMX_F_HEADER if rank == 0 else 0) | (DMX_F_FINAL if rank == world - 1 else 0)
+
+
+def shard_flags_bgzf(rank: int, world: int) -> int:
+    """DMX_F_BGZF shards: every member frames itself, so no shard carries stream framing and
+    the pieces concatenate with nothing between them (no sync flush, no host trailer); the last
+    shard appends the end-of-file member (DMX_F_FINAL)."""
+    return DMX_F_BGZF | (DMX_F_FINAL if rank == world - 1 else 0)
 
 
 def combine_adler(adlers, lengths) -> int:

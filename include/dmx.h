@@ -44,8 +44,9 @@ void deflate_compr_deinit(deflate_compr_t* com);
 /* deflate_ext.h:17, impl deflate_compress.c:362-376.
  * Reads fd_in to EOF, writes a zlib stream (RFC 1950/1951) to fd_out -- or, with
  * DMX_FORMAT=gzip in the environment, one gzip member (RFC 1952) around the same DEFLATE
- * data; unset or "zlib" is the zlib stream, any other value returns -E_INVAL before anything
- * is read or written -- and if
+ * data, or with DMX_FORMAT=bgzf a BGZF file (DMX_F_BGZF: a gzip member per sw block and the
+ * end-of-file member; with DMX_DICT or DMX_SPLIT that is -E_INVAL); unset or "zlib" is the zlib
+ * stream, any other value returns -E_INVAL before anything is read or written -- and if
  * fd_stats >= 0 one 24-byte struct compress_stats per token.  sw = block size /
  * window (1..32768; 0 means 32768).  ops is unused (as in the reference).
  * The parse is the reference's: exhaustive hash-chain search, greedy, longest
@@ -145,6 +146,25 @@ struct compress_stats {
                             trailer is written (shards: dmx_result.adler, dmx_crc32_combine).
                             The DEFLATE data is bit for bit that of the zlib stream. */
 #define DMX_GZIP (DMX_ZLIB | DMX_F_GZIP)
+#define DMX_F_BGZF 1024u /* container option: BGZF (SAM/BAM specification §4.1), blocked gzip -- every
+                            sw block becomes a complete gzip member of its own: an 18-byte header
+                            (1F 8B 08 04, mtime 0, XFL 0, OS 255, XLEN 6, the "BC" subfield with
+                            BSIZE = member size - 1), the block's DEFLATE data from a byte boundary
+                            with BFINAL set and zero bits up to the next one, then the CRC-32
+                            (per block, csrc/dmx_crc.hip) and byte count of the block.  The DEFLATE
+                            data is that of the zlib stream of the block alone (same parse, block
+                            type and codes).  DMX_F_HEADER, DMX_F_TRAILER and DMX_F_GZIP are
+                            ignored: every member frames itself.  DMX_F_FINAL appends the 28-byte
+                            end-of-file member; without it nothing follows the last member (no
+                            sync flush: members concatenate as they are).  An empty input gives the
+                            end-of-file member alone, or nothing.  Any gzip reader decompresses
+                            the output; dmx_bgzf_index finds the members for the GPU inflate.
+                            DMX_F_DICT (members would depend on each other) and DMX_F_SPLIT (left
+                            out so far) return -E_INVAL with it.  dmx_result: adler is 0 (no
+                            stream-wide check value), end_bits = 8 x the offset just past the last
+                            data member, out_len includes the end-of-file member.  dmx_block_index:
+                            bit = first bit of the member's DEFLATE data, 8 x (member offset + 18). */
+#define DMX_BGZF (DMX_F_BGZF | DMX_F_FINAL)
 #define DMX_F_EXACT_SORT 16u  /* test hook: sort positions with the match-any grouping instead
                                 of lane-ordered LDS atomics (same result; used by the tests) */
 #define DMX_F_LAZY 8u    /* parse option: lazy evaluation, one position of
@@ -222,7 +242,8 @@ int dmx_ctx_reserve(dmx_ctx* ctx, uint64_t n, int32_t sw);
 int dmx_ctx_reserve_flags(dmx_ctx* ctx, uint64_t n, int32_t sw, uint32_t flags);
 /* Worst-case output bytes for n input bytes with block size sw. */
 uint64_t dmx_max_compressed(uint64_t n, int32_t sw);
-/* The same for the container `flags` select: 12 bytes more under DMX_F_GZIP. */
+/* The same for the container `flags` select: 12 bytes more under DMX_F_GZIP; under DMX_F_BGZF
+ * 26 bytes more per block (18 + 8 of each member) and 28 for the end-of-file member. */
 uint64_t dmx_max_compressed_flags(uint64_t n, int32_t sw, uint32_t flags);
 
 /* Enqueue the whole encode of device buffer d_in[0..n) into d_out (capacity
@@ -254,8 +275,10 @@ int dmx_encode_host(const uint8_t* in, uint64_t n, uint8_t* out, uint64_t out_ca
  * (chunks joined by sync flushes, Adler-32 combined on the host; DMX_F_DICT carries the
  * history across chunks).  opts->flags: the parse/block options (DMX_F_LAZY, _SPLIT, _DICT)
  * and DMX_F_GZIP (one gzip member: chunk 0 carries the gzip header, the chunks' CRC-32s are
- * combined on the host, which writes CRC-32 and the byte count mod 2^32 at the end); the rest
- * of the framing is its own.  Returns 0 or -E_*. */
+ * combined on the host, which writes CRC-32 and the byte count mod 2^32 at the end) or
+ * DMX_F_BGZF (the chunks' members concatenated as they are -- the chunk size is a multiple of
+ * sw, so the block cuts do not depend on it -- and the end-of-file member once, behind the last
+ * chunk; nothing is combined on the host); the rest of the framing is its own.  Returns 0 or -E_*. */
 int dmx_encode_fd(int fd_in, int fd_out, const dmx_opts* opts, uint64_t chunk);
 
 /* Where the last single-device dmx_encode_fd call (or deflate_compress without fd_stats)
@@ -340,6 +363,20 @@ int dmx_inflate_chained_async(const void* d_z, uint64_t zbytes, const dmx_iblock
  * synchronizes the stream).  Returns 0 or -E_*. */
 int dmx_inflate_chained_lists(const void* d_work, uint32_t* host, uint32_t n, void* stream);
 
+/* The block index of a BGZF file in host memory (DMX_F_BGZF output, or any BGZF file whose
+ * members hold at most 32768 bytes of input each -- htslib's default 65280-byte blocks are out
+ * of range for the one-wave-per-block decoder): walks the members by the BSIZE of their "BC"
+ * FEXTRA subfield (other subfields may precede or follow it) and emits one entry per member with
+ * ISIZE > 0 -- bit = first bit of its DEFLATE data, out_off = the sum of the ISIZEs before it,
+ * out_len = ISIZE -- and the member's stored CRC-32 into crc[] (may be NULL); empty members, the
+ * end-of-file one included, give no entry.  *nblk receives the number of entries (also when cap
+ * is too small), *out_len the total of the ISIZEs.  The entries are input for dmx_inflate_async
+ * once copied to the device (a member may hold several DEFLATE blocks: the decoder runs to
+ * BFINAL).  Returns 0, -E_ZHEAD (a member is not gzip / deflate or has no BC subfield), -E_LEN
+ * (truncated), -E_SZ (cap too small), -E_RANGE (a member with ISIZE > 32768).  Host only. */
+int dmx_bgzf_index(const uint8_t* z, uint64_t zlen, dmx_iblock* idx, uint32_t* crc, uint32_t cap, uint32_t* nblk,
+                   uint64_t* out_len);
+
 /* Introspection of the last encode of ctx (tests / fd_stats): per-block token
  * counts and the token stream (t = byte | dist << 9 | len),
  * per-block BTYPE, and the lit/len + distance code lengths (286 + 30 per block). */
@@ -395,6 +432,13 @@ uint32_t dmx_adler32_combine(uint32_t a, uint32_t b, uint64_t len_b);
  * (dmx_ctx_reserve), and calls that share a context -- DMX_F_GZIP encodes included -- must be
  * ordered on one stream.  Returns 0 or -E_*. */
 int dmx_crc32_async(dmx_ctx* ctx, const void* d_in, uint64_t n, uint32_t* d_crc, void* stream);
+/* Enqueue the CRC-32 of every sw-byte block of d_in[0..n) (the last one may be short) on
+ * `stream`: d_crc[b] (4-byte aligned, ceil(n / sw) words) receives block b's finished value.
+ * d_in may have any alignment, sw is 1..32768 (0 = 32768; else -E_RANGE).  One launch, no
+ * allocation, no host synchronisation (graph-capturable), and no scratch of the context: calls
+ * need no ordering against other work of the context.  Reads whole 16-byte groups as
+ * dmx_crc32_async does.  -E_SZ when there are 2^31 blocks or more.  Returns 0 or -E_*. */
+int dmx_crc32_blocks_async(dmx_ctx* ctx, const void* d_in, uint64_t n, int32_t sw, uint32_t* d_crc, void* stream);
 /* CRC-32 combine: crc of A||B from crc(A), crc(B), len(B).  Host only. */
 uint32_t dmx_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
 /* The CRC kernel's geometry (tests): bytes per workgroup span and per lane slice. */
