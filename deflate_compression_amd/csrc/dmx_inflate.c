@@ -211,7 +211,8 @@ static int dynamic(ist* s) {
     memset(len, 0, sizeof(len));
     for (int k = 0; k < ncode; k++) len[order[k]] = (uint8_t)bits(s, 3);
     if (s->err) return s->err;
-    if (build(&lh, len, 19) != 0) return -(int)E_HUFAMB;
+    /* the code length code must be complete (an empty one is not a code either) */
+    if (build(&lh, len, 19) != 0 || lh.count[0] == 19) return -(int)E_HUFAMB;
     int idx = 0;
     while (idx < nlen + ndist) {
         int sym = decode(s, &lh);
@@ -235,10 +236,12 @@ static int dynamic(ist* s) {
         }
     }
     if (len[256] == 0) return -(int)E_ZINV;
+    /* an incomplete code is allowed only as a single code of length 1 (zlib's rule and puff's);
+     * a distance table without any code is legal until a length symbol needs it (-E_HUFINV) */
     int e = build(&lh, len, nlen);
-    if (e < 0 || (e > 0 && nlen - lh.count[0] != 1)) return -(int)E_HUFAMB;
+    if (e < 0 || (e > 0 && !(nlen - lh.count[0] == 1 && lh.count[1] == 1))) return -(int)E_HUFAMB;
     e = build(&dh, len + nlen, ndist);
-    if (e < 0 || (e > 0 && ndist - dh.count[0] != 1)) return -(int)E_HUFAMB;
+    if (e < 0 || (e > 0 && !(ndist - dh.count[0] == 1 && dh.count[1] == 1))) return -(int)E_HUFAMB;
     return codes(s, &lh, &dh);
 }
 

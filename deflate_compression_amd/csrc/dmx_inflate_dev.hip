@@ -120,8 +120,20 @@ __device__ __forceinline__ void ib_refill(IBits& r) {   // afterwards bc >= 32
         r.bc += 32;
     }
 }
-// a word read that starts 8 or more bytes past the end of the stream (word wi - 1 was the last read)
-__device__ __forceinline__ bool ib_over(const IBits& r) { return (uint64_t)r.wi * 4 >= (uint64_t)r.hi + 12; }
+// Bits consumed so far and bits the stream has (both from zb).  The reader hands out zeros past
+// the end, so a decode that ran out of input is seen afterwards, exactly: used > have.
+__device__ __forceinline__ uint64_t ib_used(const IBits& r) { return (uint64_t)r.wi * 32 - r.bc; }
+__device__ __forceinline__ uint64_t ib_have(const IBits& r) { return (uint64_t)r.hi * 8; }
+__device__ __forceinline__ bool ib_past(const IBits& r) { return ib_used(r) > ib_have(r); }
+// The status of a block that returned err (0 or -E_*), as the host decoder reports it
+// (dmx_inflate.c; the table in include/dmx.h): input that ended before the block did is -E_LEN
+// whatever the zeros behind it decoded to, and a bit pattern that is no code is -E_HUFINV only
+// where the 15 bits that show it are all there (the pattern itself is not consumed).
+__device__ __forceinline__ int ib_status(const IBits& r, int err) {
+    if (ib_past(r)) return -(int)E_LEN;
+    if (err == -(int)E_HUFINV && ib_used(r) + 15 > ib_have(r)) return -(int)E_LEN;
+    return err;
+}
 __device__ __forceinline__ void ib_seek(IBits& r, uint64_t bit) {   // bit: relative to z
     const uint64_t ab = bit + (uint64_t)r.lo * 8;
     r.wi = (uint32_t)(ab >> 5);
@@ -657,12 +669,17 @@ __device__ __forceinline__ int iblock(InfLDS<W, typename std::conditional<CELL, 
     int e = itable_build<false>(S, S.lt, gt, nlen, lane);
     [[maybe_unused]] const unsigned long long tl1 = IST_NOW();
     IST_ADD(o, 9, tl1 - tl0);
-    if (e < 0 || (e > 0 && bt == 2 && rfl(S.lt.offs[15] + S.lt.cnt[15]) != 1)) return -(int)E_HUFAMB;
+    // an incomplete code is allowed only as a single code of length 1 (offs[15] + cnt[15]: the
+    // number of codes); a distance table without any code is legal until a length needs it
+    if (e < 0 || (e > 0 && bt == 2 && !(rfl(S.lt.offs[15] + S.lt.cnt[15]) == 1 && rfl(S.lt.cnt[1]) == 1)))
+        return -(int)E_HUFAMB;
     for (int s = (int)lane; s < 32; s += 64) S.len[s] = s < ndist ? S.seq[nlen + s] : 0;
     __syncthreads();
     e = itable_build<true>(S, S.dt, gt + (1u << IFB), ndist, lane);
     IST_ADD(o, 10, IST_NOW() - tl1);
-    if (e < 0 || (e > 0 && bt == 2 && rfl(S.dt.offs[15] + S.dt.cnt[15]) > 1)) return -(int)E_HUFAMB;
+    if (e < 0 || (e > 0 && bt == 2 && rfl(S.dt.offs[15] + S.dt.cnt[15]) != 0 &&
+                  !(rfl(S.dt.offs[15] + S.dt.cnt[15]) == 1 && rfl(S.dt.cnt[1]) == 1)))
+        return -(int)E_HUFAMB;
 
     // symbols: the common path in isym_run (literals, lengths and distances with table codes,
     // matches inside the ring without overlap or with a period >= 64); the rest here.
@@ -732,8 +749,12 @@ __device__ __forceinline__ int iblock(InfLDS<W, typename std::conditional<CELL, 
             ib_refill(r);
             uint32_t ed = rfl(gtab_ld(gt + (1u << IFB) + ib_peek(r, IFB)));
             if (ed >= IVBAD) {
+                // no code at the reader (an unused code of an incomplete table, a table without
+                // codes, the fixed code's 30 and 31): -E_HUFINV; -E_HUFVAL is a decoded symbol
+                // out of range, which no distance table of at most 30 symbols can produce
                 const uint32_t e16 = ed == IVSLOW ? ientry_slow(r, S.dt) : ISLOW;
-                ed = e16 == ISLOW ? IVBAD : iv_d(e16);
+                if (e16 == ISLOW) { err = -(int)E_HUFINV; break; }
+                ed = iv_d(e16);
                 if (ed == IVBAD) { err = -(int)E_HUFVAL; break; }
             }
             dist = iv_dbase(ed) + iv_extra(r.bb, ed);
@@ -796,9 +817,7 @@ __device__ __forceinline__ int iblock(InfLDS<W, typename std::conditional<CELL, 
     }
     o.op = op;
     IST_ADD(o, 1, IST_NOW() - ts1);
-    if (err) return err;
-    if (ib_over(r)) return -(int)E_LEN;
-    return 0;
+    return err;   // (the caller folds the end of the input in: ib_status)
 }
 
 // CELL: out is the cell buffer (2 bytes a position), out_cap in positions
@@ -837,7 +856,7 @@ __global__ __launch_bounds__(64) void dmx_inflate_index_kernel(const uint8_t* __
         ib_seek(r, bit);
         bool last = false;
         do {   // one sw block may be several DEFLATE blocks (DMX_F_SPLIT)
-            err = iblock<true, false, WR, CELL>(S, r, o, gt, lane, last);
+            err = ib_status(r, iblock<true, false, WR, CELL>(S, r, o, gt, lane, last));
         } while (!err && o.op < olen && !last);
         if (!err && o.op != olen) err = -(int)E_SZ;
         if (!err) io_flush<false>(S, o, o.op, lane);
@@ -870,7 +889,7 @@ __global__ __launch_bounds__(64) void dmx_inflate_stream_kernel(const uint8_t* _
     o.a = 1;
     o.b = 0;
     int err = 0;
-    if (zbytes < 6) err = -(int)E_ZHEAD;
+    if (zbytes < 2) err = -(int)E_ZHEAD;   // (a header and nothing behind it: -E_LEN at the first block)
     if (!err) {
         const uint32_t cmf = z[0], flg = z[1];
         if ((cmf & 0x0F) != 8) err = -(int)E_ZCMPMT;
@@ -881,14 +900,14 @@ __global__ __launch_bounds__(64) void dmx_inflate_stream_kernel(const uint8_t* _
     if (!err) {
         ib_seek(r, 16);
         bool last = false;
-        while (!err && !last) err = iblock<true, true, IW>(S, r, o, gtab, lane, last);
+        while (!err && !last) err = ib_status(r, iblock<true, true, IW>(S, r, o, gtab, lane, last));
     }
     if (!err) {
         io_flush<true>(S, o, o.op, lane);
         ib_drop(r, r.bc & 7);   // Adler-32 trailer, MSB first
         uint32_t want = 0;
         for (int k = 0; k < 4; k++) want = (want << 8) | ib_bits(r, 8);
-        if (ib_over(r)) err = -(int)E_LEN;
+        if (ib_past(r)) err = -(int)E_ZADL32;   // cut inside the trailer
         else if (((o.b << 16) | o.a) != want) err = -(int)E_ZADL32;
     }
     if (lane == 0) {

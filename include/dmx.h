@@ -62,7 +62,23 @@ int deflate_compress(int fd_in, int fd_out, int fd_stats, swi sw, int ops);
  * FEXTRA / FNAME / FCOMMENT / FHCRC fields skipped, CRC-32 (-E_CRC) and ISIZE (-E_LEN)
  * checked, bytes after the first member ignored) into a malloc'd decompr_dat->str that the
  * caller frees.  ops & DEFLATE_NULLTERM appends a '\0' (not counted in len).
- * Returns 0 or -E_*. */
+ * Returns 0 or -E_*.  zlib decides what is a stream; a rejected one has this status, the same
+ * from dmx_inflate_async's stream mode (tests/test_inflate_conformance.py):
+ *   -E_ZHEAD    fewer than 2 bytes (or a gzip header cut short)
+ *   -E_ZCMPMT / -E_ZSLWIN / -E_ZFCHCK / -E_ZPDICT   the zlib header: CM, CINFO, FCHECK, FDICT
+ *   -E_LEN      the input ends inside the DEFLATE data, whatever would have followed
+ *   -E_ZBTYPE   BTYPE 3;   -E_ZNLEN  stored LEN != ~NLEN
+ *   -E_ZINV     HLIT > 286, HDIST > 30, a 16 with no length before it, a repeat past
+ *               HLIT + HDIST, no code for the end of block
+ *   -E_HUFAMB   an over-subscribed code, or an incomplete one: the code length code must be
+ *               complete; a literal/length or distance code may be incomplete only as a single
+ *               code of length 1; a distance table without codes is legal until a length needs it
+ *   -E_HUFINV   a bit pattern that is no code (the unused code of a single-code table, a length
+ *               with an empty distance table, the fixed distance symbols 30 / 31), where the 15
+ *               bits that show it are there (else -E_LEN)
+ *   -E_HUFVAL   a decoded symbol out of range: the fixed code's 286 / 287
+ *   -E_HUFDIS   a distance before the first output byte
+ *   -E_ZADL32   a wrong Adler-32 or a stream cut inside it; bytes after the trailer are ignored */
 int deflate_decompress(struct string_len* decompr_dat, struct string_len* compr_dat, int ops);
 
 /* deflate_ext.h:19-31 -- per-token record written to fd_stats.
@@ -342,7 +358,13 @@ int dmx_block_index(dmx_ctx* ctx, dmx_iblock* d_index, uint32_t cap, void* strea
  * record d_status.  The first-level tables live in device scratch taken from a per-device
  * stream-ordered pool on every call (hipMallocFromPoolAsync before the launch, hipFreeAsync
  * after it on the same stream).  Returns 0 or -E_*: -E_MALLOC when that scratch cannot be
- * allocated, -E_DEVICE for launch errors. */
+ * allocated, -E_DEVICE for launch errors.
+ * d_status->status of the stream mode is deflate_decompress's status for the same bytes (the
+ * table above), and -E_SZ when out_cap is too small.  The indexed mode has no header or
+ * trailer: it reports the same status for an error that precedes a block's output (tables,
+ * block headers, a first symbol), the status of whichever limit comes first otherwise, -E_SZ
+ * for a block that ends short of or beyond its out_len and -E_RANGE for an entry outside the
+ * stream or the output (out_len above 32768 included). */
 int dmx_inflate_async(const void* d_z, uint64_t zbytes, const dmx_iblock* d_index, uint32_t nblk, void* d_out,
                       uint64_t out_cap, dmx_inflate_status* d_status, void* stream);
 

@@ -57,6 +57,12 @@ def test_code_lengths_match_oracle(enc, golden_cases):
         if bt == 2:
             ln = enc.code_lengths(0)
             assert np.array_equal(ln[:286], lll) and np.array_equal(ln[286:], ld), name
+            # no incomplete code leaves the encoder (the decoders allow one only as a single code
+            # of length 1): a lone used symbol gets a partner, two codes of length 1
+            for t in (ln[:286], ln[286:]):
+                assert not t.any() or sum(1 << (15 - int(x)) for x in t if x) == 1 << 15, name
+            if name == "zeros32k":   # one distance in use
+                assert sorted(int(x) for x in ln[286:] if x) == [1, 1]
 
 
 @pytest.mark.parametrize("kind,n", [("bee", 57641), ("text", 1 << 20), ("zeros", 1 << 20), ("random", 300000),
