@@ -18,9 +18,10 @@
 //                         codes, RFC 1951 §3.2.7 header, exact stored/fixed/
 //                         dynamic cost, BTYPE choice (replaces the reference's
 //                         per-token estimators aht.c / h_tree.c).
-//   K3  dmx_scan_kernel   one workgroup: bit offsets of all blocks (a scan over an
-//                         associative "stored blocks re-align" monoid), Adler-32
-//                         combine, zlib header / flush / trailer, boundary words.
+//   K3  dmx_scan_*        bit offsets of all blocks (a scan over an associative
+//                         "stored blocks re-align" monoid, per tile of 256 blocks,
+//                         then over the tiles), Adler-32 combine, dmx_result and
+//                         -E_SZ, the boundary words zeroed (see "K3, the stream layout").
 //   K4  dmx_pack_kernel   one 256-thread workgroup per block: bit-packs header +
 //                         tokens (or the stored bytes) at the block's absolute bit
 //                         offset in LDS, then coalesced 32-bit stores to HBM.
@@ -886,14 +887,10 @@ __device__ __forceinline__ uint32_t search_quads(MatchLDS& L, uint32_t bn, uint3
     constexpr uint32_t OWN = 4 * (64 - HQ);
     const uint32_t lane = tid & 63, wave = wave_of(tid);
     const uint32_t nvalid = bn > 2 ? bn - 2 : 0;
-#ifndef DMX_QSLOTS
     // the extension queue: a ring of 128 items per wave over tsm + exitp (both free during the
     // search, adjacent in MatchLDS): a chunk's items go in at once, batches of 64 come out
     uint32_t* Qw = L.tsm + (wave << 7);
     uint32_t qh = 0;   // ring head (wave-uniform)
-#else
-    uint32_t* Qw = L.tsm + (wave << 6);   // the extension queue (P2 arrays are free during the search)
-#endif
     const uint64_t lt = (1ull << lane) - 1ull;
     uint32_t qn = 0, iters = 0;
     uint32_t cnext = wave_claim(&L.ntok);   // chunks from the workgroup counter, one ahead (search_pairs)
@@ -956,7 +953,6 @@ __device__ __forceinline__ uint32_t search_quads(MatchLDS& L, uint32_t bn, uint3
         }
         // a candidate equal in all CBS bytes (key >= 64): the entry is queued for the LDS
         // extension (unless the block end caps it there); E_0's items, then E_1's, ...
-#ifndef DMX_QSLOTS
         bool push[4];
         uint64_t pmv[4];
         uint32_t npr[4];
@@ -1003,40 +999,6 @@ __device__ __forceinline__ uint32_t search_quads(MatchLDS& L, uint32_t bn, uint3
                 rs = rs >= 3u ? 5u : rs + 1u;
             }
         }
-#else
-        bool push[4];
-        uint64_t pmv[4];
-        uint32_t pbits = 0, jbits = 0;   // per slot r: push flag (bit r), the key's 8 - j (bits 3r + 2 .. 3r)
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-#ifdef DMX_KO_QUEUE   // timing knockout (wrong output): no queued extension
-            push[r] = false;
-#else
-            push[r] = act[r] && key[r] >= (CBS << 3) && lim[r] > CBS;
-#endif
-            pmv[r] = __ballot(push[r]);
-            pbits |= push[r] ? 1u << r : 0u;
-            jbits |= (key[r] & 7u) << (3 * r);
-        }
-        const uint32_t npt = (uint32_t)(__popcll(pmv[0]) + __popcll(pmv[1]) + __popcll(pmv[2]) + __popcll(pmv[3]));
-        if (npt || (!more && qn)) {
-#pragma nounroll
-            for (uint32_t h = 0; h < 4; h++) {   // (one call site of ext_queue)
-                const uint64_t pm = h == 0 ? pmv[0] : h == 1 ? pmv[1] : h == 2 ? pmv[2] : pmv[3];   // (scalar selects)
-                const uint32_t npx = (uint32_t)__popcll(pm);
-                if (qn + npx > 64 || (!more && qn)) {
-                    const uint64_t td0 = stamp ? __builtin_amdgcn_s_memtime() : 0;
-                    ext_queue<DICT, false>(L, bn, KK, Qw, qn, lane, hbk);
-                    if (stamp) tdef += __builtin_amdgcn_s_memtime() - td0;
-                    qn = 0;
-                }
-                if (!more) break;
-                if ((pbits >> h) & 1u)
-                    lds_st(&Qw[qn + (uint32_t)__popcll(pm & lt)], (k0 + h) | ((8u - ((jbits >> (3 * h)) & 7u)) << 15));
-                qn += npx;
-            }
-        }
-#endif
         if (!more) break;
         uint32_t nib = 0;
 #pragma unroll
@@ -1058,19 +1020,11 @@ __device__ __forceinline__ uint32_t search_positions(MatchLDS& L, uint32_t bn, i
     const uint32_t nvalid = bn > 2 ? bn - 2 : 0;   // positions with a full trigram = entries of S
     uint32_t iters = 0;
     if (RUNS) build_chg(L, bn, tid);
-#ifndef DMX_NO_PAIRS
-    if (!RUNS && NB == 3 && K >= 6 && K <= 8) {
-#ifndef DMX_PAIRS   // four entries per lane (search_quads; DMX_PAIRS: the round-5 two-entry path)
+    if (!RUNS && NB == 3 && K >= 6 && K <= 8) {   // four entries per lane
         iters = K == 8 ? search_quads<DICT, 8>(L, bn, tid, stamp, tdef, hbk)
               : K == 7 ? search_quads<DICT, 7>(L, bn, tid, stamp, tdef, hbk)
                        : search_quads<DICT, 6>(L, bn, tid, stamp, tdef, hbk);
-#else   // two entries per lane (search_pairs)
-        iters = K == 8 ? search_pairs<DICT, 8>(L, bn, tid, stamp, tdef, hbk)
-              : K == 7 ? search_pairs<DICT, 7>(L, bn, tid, stamp, tdef, hbk)
-                       : search_pairs<DICT, 6>(L, bn, tid, stamp, tdef, hbk);
-#endif
     } else
-#endif
     if (K <= KE) {
         // bounded mode with a short chain: chunks of 64-K owned entries, halo embedded.
         // Entries with a candidate equal in all CBS register bytes need the LDS extension; they
@@ -1325,7 +1279,6 @@ __device__ __forceinline__ uint32_t resolve_word(const MatchLDS& L, uint32_t lo,
     if (e >= lo + 32 || e >= bn) { nm_out = 0; return e; }
     uint32_t nm = 0, p = e;
     while (p < lo + 32 && p < bn) {
-#ifndef DMX_WALK_STEP
         // a run of literals in one step (their bits in lw, up to the segment end or bn): every
         // position of it is a token start; no LDS read
         const uint32_t sh = p - lo;
@@ -1346,12 +1299,6 @@ __device__ __forceinline__ uint32_t resolve_word(const MatchLDS& L, uint32_t lo,
         if (m & bit) { nm_out = nm | (m & ~(bit - 1u)); merged = true; return x; }
         nm |= bit;
         p += (uint32_t)L.len8[p] + 3u;
-#else
-        const uint32_t bit = 1u << (p - lo);
-        if (m & bit) { nm_out = nm | (m & ~(bit - 1u)); merged = true; return x; }
-        nm |= bit;
-        p += ((lw >> (p - lo)) & 1u) ? 1u : (uint32_t)L.len8[p] + 3u;
-#endif
     }
     nm_out = nm;
     return p;
@@ -1457,7 +1404,7 @@ __device__ __forceinline__ uint32_t atomic_rank16(uint32_t* T, uint32_t v, bool 
 // Bucket-sorted positions S (stable by position inside a bucket) by ONE counting pass over
 // the 13-bit bucket (round 5; the two-pass LSD sort below stays as the checked fallback).
 // The block's positions form four groups of 8192 (g = w >> 2 for wave w; round 6: two groups
-// of 16384 until round 5, -DDMX_SORT_G2); T[h] (in len8) holds the counts of bucket h of groups
+// of 16384 until round 5); T[h] (in len8) holds the counts of bucket h of groups
 // 0 and 1 in its low and high 16 bits, T2[h] (in S's first half, free until the scatter)
 // those of groups 2 and 3.
 //  1. every wave hashes its 2048 positions [2048w, 2048w + 2048) into registers;
@@ -1485,7 +1432,6 @@ __device__ __forceinline__ void count_sort_positions(MatchLDS& L, uint32_t bn, i
     const uint4 z4 = make_uint4(0, 0, 0, 0);
     reinterpret_cast<uint4*>(T)[tid] = z4;
     reinterpret_cast<uint4*>(T)[tid + MT] = z4;
-#ifndef DMX_SORT_G2
     // four groups of four waves: groups 2 and 3 count in the first half of S (free until the
     // scatter), four ordered rounds of four waves instead of eight of two
     uint32_t* T2 = reinterpret_cast<uint32_t*>(L.sorted);
@@ -1494,11 +1440,6 @@ __device__ __forceinline__ void count_sort_positions(MatchLDS& L, uint32_t bn, i
     constexpr uint32_t NR = 4;
     uint32_t* Tg = (wave >> 3) ? T2 : T;
     const uint32_t sh = ((wave >> 2) & 1) << 4;   // this wave's group field
-#else
-    constexpr uint32_t NR = 8;
-    uint32_t* Tg = T;
-    const uint32_t sh = (wave >> 3) << 4;   // this wave's group field
-#endif
     __syncthreads();   // (also: the staged block, for callers without a barrier after staging)
     const uint64_t lt = (1ull << lane) - 1ull;
     uint32_t x0l = (wave << 11) + lane, nvl = nvalid;
@@ -1554,44 +1495,33 @@ __device__ __forceinline__ void count_sort_positions(MatchLDS& L, uint32_t bn, i
     {   // bucket starts: thread t scans buckets 8t .. 8t + 7
         const uint4 a = reinterpret_cast<const uint4*>(T)[2 * tid], c = reinterpret_cast<const uint4*>(T)[2 * tid + 1];
         uint32_t w[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w}, pre[8], s = 0;
-#ifndef DMX_SORT_G2
         const uint4 a2 = reinterpret_cast<const uint4*>(T2)[2 * tid], c2 = reinterpret_cast<const uint4*>(T2)[2 * tid + 1];
         uint32_t w2[8] = {a2.x, a2.y, a2.z, a2.w, c2.x, c2.y, c2.z, c2.w};
-#endif
 #pragma unroll
         for (int j = 0; j < 8; j++) {
             pre[j] = s;
             s += (w[j] & 0xFFFFu) + (w[j] >> 16);
-#ifndef DMX_SORT_G2
             s += (w2[j] & 0xFFFFu) + (w2[j] >> 16);
-#endif
         }
         const uint32_t base = block_excl_scan(L, s, tid);
 #pragma unroll
         for (int j = 0; j < 8; j++) {
             const uint32_t st0 = base + pre[j];
             pre[j] = st0;
-#ifndef DMX_SORT_G2
             const uint32_t s1 = st0 + (w[j] & 0xFFFFu), s2 = s1 + (w[j] >> 16);
             w[j] = st0 | (s1 << 16);
             w2[j] = s2 | ((s2 + (w2[j] & 0xFFFFu)) << 16);
-#else
-            w[j] = st0 | ((st0 + (w[j] & 0xFFFFu)) << 16);
-#endif
         }
         reinterpret_cast<uint4*>(T)[2 * tid] = make_uint4(w[0], w[1], w[2], w[3]);
         reinterpret_cast<uint4*>(T)[2 * tid + 1] = make_uint4(w[4], w[5], w[6], w[7]);
-#ifndef DMX_SORT_G2
         reinterpret_cast<uint4*>(T2)[2 * tid] = make_uint4(w2[0], w2[1], w2[2], w2[3]);
         reinterpret_cast<uint4*>(T2)[2 * tid + 1] = make_uint4(w2[4], w2[5], w2[6], w2[7]);
-#endif
         if (need_starts)
             reinterpret_cast<uint4*>(L.bstart)[tid] = make_uint4(pre[0] | (pre[1] << 16), pre[2] | (pre[3] << 16),
                                                                  pre[4] | (pre[5] << 16), pre[6] | (pre[7] << 16));
     }
     __syncthreads();
     asm volatile("" : "+v"(x0l), "+v"(nvl));
-#ifndef DMX_SORT_G2
     // the destinations first (groups 2 and 3 read theirs from S's first half), then the stores
 #pragma unroll
     for (int st = 0; st < 32; st++) {
@@ -1607,16 +1537,6 @@ __device__ __forceinline__ void count_sort_positions(MatchLDS& L, uint32_t bn, i
         const uint32_t x = x0l + ((uint32_t)st << 6);
         if (x < nvl) L.sorted[(rk[st >> 1] >> (16 * (st & 1))) & 0xFFFFu] = (uint16_t)x;
     }
-#else
-#pragma unroll
-    for (int st = 0; st < 32; st++) {
-        const uint32_t x = x0l + ((uint32_t)st << 6);
-        const uint32_t h = (hh[st >> 1] >> (16 * (st & 1))) & 0xFFFFu;
-        const uint32_t rr = (rk[st >> 1] >> (16 * (st & 1))) & 0xFFFFu;
-        if (x < nvl) L.sorted[((T[h] >> sh) & 0xFFFFu) + rr] = (uint16_t)x;
-        if ((st & 7) == 7) __builtin_amdgcn_sched_barrier(0);
-    }
-#endif
     __syncthreads();
     if (stamp && tid == 0) tp0[2] = __builtin_amdgcn_s_memtime();
 }
@@ -1643,12 +1563,10 @@ __device__ __forceinline__ void count_sort_positions(MatchLDS& L, uint32_t bn, i
 template <bool EXACT, bool RUNCHK = true, int NB = 3>
 __device__ __forceinline__ void sort_positions(MatchLDS& L, uint32_t bn, int32_t max_chain, uint32_t tid, bool stamp,
                                                uint64_t* tp0) {
-#ifndef DMX_OLD_SORT
     if constexpr (!EXACT) {
         count_sort_positions<RUNCHK, NB>(L, bn, max_chain, tid, stamp, tp0);
         return;
     }
-#endif
     const uint32_t lane = tid & 63, wave = wave_of(tid);
     const uint32_t nvalid = bn > 2 ? bn - 2 : 0;   // positions with a full trigram
     const bool need_starts = max_chain <= 0 || max_chain > KD;
@@ -1788,11 +1706,7 @@ __device__ __forceinline__ void sort_positions(MatchLDS& L, uint32_t bn, int32_t
 template <int NG>
 __device__ __forceinline__ uint32_t gram_pass(MatchLDS& L, uint32_t nv, uint32_t tid, uint16_t* __restrict__ seeds,
                                               uint32_t& ndefer, uint64_t& tsweep) {
-#ifndef DMX_GRAM_PW
     constexpr uint32_t PW = 9;
-#else
-    constexpr uint32_t PW = DMX_GRAM_PW;   // (diagnostic builds)
-#endif
     constexpr uint32_t GM = NG == 3 ? 0xFFFFFFu : 0xFFFFFFFFu;
     const uint32_t lane = tid & 63;
     uint32_t* UL = L.tsm;   // tsm + exitp: 2048 slots, free until the next sort
@@ -1837,11 +1751,7 @@ __device__ __forceinline__ uint32_t gram_pass(MatchLDS& L, uint32_t nv, uint32_t
             }
         }
         // (a gram that runs past the block's end is a match of fewer bytes: the 3-byte seed stays)
-#ifndef DMX_H4_NOSTORE
         if (act && (NG == 3 || (q != 0xFFFFu && i + NG <= nv + 2))) seeds[i] = seed_enc<NG>(q);
-#else
-        if (act && q == 0x1234u) seeds[i] = (uint16_t)q;   // (diagnostic timing builds: the output is wrong)
-#endif
     }
     __syncthreads();
     tsweep += __builtin_amdgcn_s_memtime();   // (diagnostic stamps: the sweep's end)
@@ -3115,11 +3025,7 @@ __device__ __forceinline__ void match_block(const uint32_t b, const uint8_t* __r
     // right after the noise check's record, so the two HBM latencies overlap (a stored
     // block's are wasted: such blocks take the work-list loop when they are most of the input)
     const uint32_t pst = info[b].prestored;   // (read unconditionally: a conditional read is waited for at once)
-#ifndef DMX_LATE_STAGE   // (A/B build: the loads after the check, in the staging loop)
     constexpr bool early = !LOOP;
-#else
-    constexpr bool early = false;
-#endif
     uint4 v0 = make_uint4(0, 0, 0, 0), v1 = v0;
     if (early) {
         v0 = stage16(d, tid << 4, bn, aligned16);
@@ -3135,16 +3041,6 @@ __device__ __forceinline__ void match_block(const uint32_t b, const uint8_t* __r
     if (dbg && tid == 0) { st_search = 0; st_iters = 0; st_def = 0; st_p3a = 0; }
     for (uint32_t k = tid; k < DMX_HIST; k += MT) L.hist[k] = 0;
     for (uint32_t k = tid; k < DMX_BLK / 32; k += MT) L.lit[k] = 0;
-#ifdef DMX_PF
-    // L2 prefetch of the block DMX_PF blocks ahead (the one that takes this CU's slot next when
-    // the blocks take about the same time; same XCD: DMX_PF is a multiple of 8): one dword per
-    // 128-byte line, its value consumed after P0 so the load never stalls the staging
-    uint32_t pfv = 0;
-    if (!LOOP && tid < 256) {
-        const uint64_t po = (uint64_t)(b + DMX_PF) * sw + (uint64_t)tid * 128;
-        if (po < n) pfv = *reinterpret_cast<const uint32_t*>(in + (po & ~3ull));
-    }
-#endif
     uint32_t runny = 0;   // 16-byte chunks of one repeated byte (run-dominated blocks)
     // a block of one repeated byte: every chunk of this thread is one repeated byte, the same
     // byte cb in all of them (0x100: none yet), and (below, after the barrier) cb is byte 0
@@ -3227,9 +3123,6 @@ __device__ __forceinline__ void match_block(const uint32_t b, const uint8_t* __r
     }
 
     if (dbg_stop(mflags, 1, info, hist_g, b, bn, tid)) return;
-#ifdef DMX_PF
-    asm volatile("" ::"v"(pfv));
-#endif
     {   // Adler-32 partial sums of this block
         uint64_t s = 0, t = 0;
         const uint32_t lo = tid << 5;   // 32 bytes per thread, read as two 16-byte vectors
@@ -3357,7 +3250,6 @@ __device__ __forceinline__ void match_block(const uint32_t b, const uint8_t* __r
         const uint32_t lo = tid << 5, lw = L.lit[tid];   // the segment's literal bits: one read
         uint32_t m = 0, p = lo;
         while (p < lo + 32 && p < bn) {
-#ifndef DMX_WALK_STEP
             // a run of literals in one step (resolve_word); a match reads its length
             const uint32_t sh = p - lo;
             const uint32_t run = min(ffbl_hw(~(lw >> sh)), min(lo + 32u, bn) - p);   // (lit bits past bn may be set by P1b)
@@ -3368,10 +3260,6 @@ __device__ __forceinline__ void match_block(const uint32_t b, const uint8_t* __r
             }
             m |= 1u << sh;
             p += (uint32_t)L.len8[p] + 3u;
-#else
-            m |= 1u << (p - lo);
-            p += ((lw >> (p - lo)) & 1u) ? 1u : (uint32_t)L.len8[p] + 3u;
-#endif
         }
         L.tsm[tid] = m;
         L.exitp[tid] = p;
@@ -3551,13 +3439,8 @@ __device__ __forceinline__ void match_block(const uint32_t b, const uint8_t* __r
                 if (kk >= r0) TP[kk - r0] = (uint16_t)((tid << 5) + (uint32_t)__builtin_ctz(mm));
             __syncthreads();
             if (dbg && tid == 0 && r0 == 0) st_p3a = __builtin_amdgcn_s_memtime() - t1;   // first list built
-#ifdef DMX_P3_BATCH
-            constexpr bool p3batch = true;
-#else
-            constexpr bool p3batch = h4;   // (batched loads: the exhaustive parse +0.6 %; K = 7 48.8 -> 50.1 K cycles to P3's end, round 6)
-#endif
-            if constexpr (!p3batch) {
-#ifndef DMX_P3_BRANCHY
+            // (batched loads: the exhaustive parse +0.6 %; K = 7 48.8 -> 50.1 K cycles to P3's end, round 6)
+            if constexpr (!h4) {
             for (uint32_t t = r0 + tid; t < r1; t += MT) {
                 // one path for both token kinds: the byte, length and distance slots are read
                 // together, the lit/len symbol is the byte or the length's (RFC 1951 3.2.5 by
@@ -3575,27 +3458,8 @@ __device__ __forceinline__ void match_block(const uint32_t b, const uint8_t* __r
                 }
                 tb[t] = lit ? c : (dist << 9) | len;
             }
-#else
-            for (uint32_t t = r0 + tid; t < r1; t += MT) {
-                const uint32_t p = TP[t - r0];
-                uint32_t tk;
-                if ((L.lit[p >> 5] >> (p & 31)) & 1u) {
-                    tk = D8[p];
-                    atomicAdd(&hl[tk], 1u);
-                } else {
-                    const uint32_t len = (uint32_t)L.len8[p] + 3u, dist = L.sorted[p];
-                    tk = (dist << 9) | len;
-                    uint32_t sy, eb, ev;
-                    len_sym(len, sy, eb, ev);
-                    atomicAdd(&hl[sy], 1u);
-                    dist_sym(dist, sy, eb, ev);
-                    atomicAdd(&hl[DMX_DIST0 + sy], 1u);
-                }
-                tb[t] = tk;
-            }
-#endif
             } else {
-            // DMX_P3_BATCH (and the exhaustive parse): P3B tokens per thread at a time, their LDS reads issued together (token position,
+            // the exhaustive parse: P3B tokens per thread at a time, their LDS reads issued together (token position,
             // literal word, then byte, length and distance of each, whichever it is): three
             // rounds of latency for the batch instead of three per token
             constexpr uint32_t P3B = 8;
@@ -3879,20 +3743,16 @@ __device__ void huff_lengths(K2LDS& S, const F* f, int n, int maxbits, uint8_t* 
             S.sym[rk[r]] = (uint16_t)(ck[r] & 511u);
         }
     if (lane < 32) S.blc[lane] = 0;
-#ifndef DMX_MERGE_BRANCHY
     // sentinels for the merge: no leaf past the last (two reads ahead), no node not yet made
     // (a weight is at most 32 770, so 0xFFFF is above every real one)
     if (lane < 2) S.fs[m + lane] = 0xFFFFu;
 #pragma unroll
     for (int r = 0; r < 5; r++)
         if (r * 64 + (int)lane < 288) S.nodew[r * 64 + lane] = 0xFFFFu;
-#endif
     wsync();
     K2ST(0, kt);
     const int mm = (int)m, nn = mm - 1, root = nn - 1;
     if (lane == 0) {   // two-queue merge
-        int li = 0, ni = 0;
-#ifndef DMX_MERGE_BRANCHY
         // branch-free (the sentinels stand for an empty queue: of two items left at least one
         // is real, so a sentinel never wins a compare it should lose): four unconditional
         // reads, selects for the picks and the two parent slots -- no exec-mask changes in
@@ -3915,21 +3775,6 @@ __device__ void huff_lengths(K2LDS& S, const F* f, int n, int maxbits, uint8_t* 
             H[q2] = (uint16_t)k;
             S.nodew[k] = (uint16_t)(w1 + (l2 ? A : B));
         }
-        (void)li;
-        (void)ni;
-#else
-        for (int k = 0; k < nn; k++) {
-            const uint32_t a0 = li < mm ? S.fs[li] : 0xFFFFFFFFu, a1 = li + 1 < mm ? S.fs[li + 1] : 0xFFFFFFFFu;
-            const uint32_t b0 = ni < k ? S.nodew[ni] : 0xFFFFFFFFu, b1 = ni + 1 < k ? S.nodew[ni + 1] : 0xFFFFFFFFu;
-            uint32_t w;
-            uint32_t A, B;
-            if (li < mm && a0 <= b0) { w = a0; S.lpar[li++] = (uint16_t)k; A = a1; B = b0; }
-            else { w = b0; S.up[ni++] = (uint16_t)k; A = a0; B = b1; }
-            if (li < mm && A <= B) { w += A; S.lpar[li++] = (uint16_t)k; }
-            else { w += B; S.up[ni++] = (uint16_t)k; }
-            S.nodew[k] = (uint16_t)w;
-        }
-#endif
         S.up[root] = (uint16_t)root;
     }
     wsync();
@@ -4000,17 +3845,6 @@ __device__ void huff_lengths(K2LDS& S, const F* f, int n, int maxbits, uint8_t* 
     // maxbits minus the lengths 2..maxbits whose range ends at or before i: the range ends
     // from one LDS read per lane, then broadcasts (the loop over e was a chain of dependent
     // LDS reads per symbol register)
-#ifdef DMX_LEN_LOOP   // (A/B build: the loop over e per symbol register)
-#pragma unroll
-    for (int r = 0; r < 5; r++) {
-        const int i = r * 64 + (int)lane;
-        if (i < mm) {
-            int e = maxbits;
-            while (e > 1 && i >= S.lstart[e] + S.blc[e]) e--;
-            len[S.sym[i]] = (uint8_t)e;
-        }
-    }
-#else
     const int32_t endv = (lane >= 2 && (int)lane <= maxbits) ? S.lstart[lane] + S.blc[lane] : 0x7FFFFFFF;
     int32_t cnt[NR] = {};
 #pragma unroll
@@ -4024,7 +3858,6 @@ __device__ void huff_lengths(K2LDS& S, const F* f, int n, int maxbits, uint8_t* 
         const int i = r * 64 + (int)lane;
         if (i < mm) len[S.sym[i]] = (uint8_t)(maxbits - cnt[r]);
     }
-#endif
     wsync();
     K2ST(2, kt);
 }
@@ -4222,6 +4055,11 @@ __device__ HuffRes huff_plan(K2LDS& S, uint32_t bn, bool allow_stored, uint32_t 
     return h;
 }
 
+// BFINAL of block b: the stream's last block, and every block under DMX_F_BGZF (a member each)
+__device__ __forceinline__ uint32_t block_is_final(uint32_t flags, uint32_t b, uint32_t nblk) {
+    return (((flags & DMX_F_FINAL) && b == nblk - 1) || (flags & DMX_F_BGZF)) ? 1u : 0u;
+}
+
 // The planned block's canonical codes into codes_out (global; fixed codes for BTYPE 1) and its
 // header bits (BFINAL/BTYPE + trees) into S.hdr; returns their count.  S holds huff_plan's
 // (or huff_cl's) state.  One wave.
@@ -4289,7 +4127,7 @@ __device__ __forceinline__ void huff_one(const uint32_t b, const uint32_t* __res
     if (info[b].prestored & 1u) return;   // K0 wrote the stored record (1, 3)
     const uint32_t bn = info[b].n;
     // (DMX_F_BGZF: every block ends a member of its own)
-    const uint32_t final_bit = (((flags & DMX_F_FINAL) && b == nblk - 1) || (flags & DMX_F_BGZF)) ? 1u : 0u;
+    const uint32_t final_bit = block_is_final(flags, b, nblk);
 
     [[maybe_unused]] uint64_t kt0 = K2T();
     for (int s = (int)lane; s < 288; s += 64) S.fll[s] = s < 286 ? (s == 256 ? 1u : hg[s]) : 0u;   // + end of block
@@ -4687,17 +4525,28 @@ __device__ __forceinline__ void stream_framing(uint32_t* out32, uint32_t flags, 
 #define ADL_MOD 65521u
 #define SCAN_TILE 256
 
-// K3, the stream layout, in three launches so that the per-block records are read by many
-// CUs (one workgroup reading 32 768 records of 64 B was 0.2 ms):
-//   dmx_scan_tile_kernel   per tile of 256 blocks: the blocks' layout elements (Mono: bits,
-//                          or "align then bits" for stored blocks) scanned in the tile; each
-//                          block's tile-local exclusive prefix parked in its off_bits/len_bits,
-//                          the tile aggregate and the Adler/token/type partial sums -> tiles[];
-//   dmx_scan_kernel        one workgroup: the tile aggregates -> tile prefixes, stream end,
-//                          Adler-32, out_len, status (dmx_result); zeroes the words past the
-//                          last block; an empty input gets its whole stream here;
-//   dmx_scan_apply_kernel  per tile: absolute offsets, and zero the words each block shares
-//                          with a neighbour (the pack kernel ORs those).
+// K3, the stream layout, over tiles of 256 blocks so that the per-block records are read by
+// many CUs (one workgroup reading 32 768 records of 64 B was 0.2 ms):
+//   dmx_scan_tile_kernel   per tile: the blocks' layout elements (Mono: bits, or "align then
+//                          bits" for stored blocks) scanned in the tile; each block's
+//                          tile-local exclusive prefix parked in its off_bits/len_bits, the
+//                          tile aggregate and the Adler/token/type partial sums -> tiles[];
+// then the tile aggregates are composed, the layout is finished and applied, in one of two
+// launch shapes that share every piece of that work (the functions below):
+//   dmx_scan_apply1_kernel up to SA1_MAXT tiles: a workgroup per tile composes the aggregates
+//                          itself, the last one finishes the layout, all apply;
+//   dmx_scan_kernel        (more tiles, an empty input, the scan3 hook) one workgroup composes
+//   + dmx_scan_apply_kernel  the aggregates into tile prefixes and finishes the layout -- an
+//                          empty input gets its whole stream there; then a workgroup per tile applies.
+// The layout's finish, once per encode:
+//   stream_extent          the end of the last block, the stream's end and length, and the
+//                          status: the one place that decides -E_SZ (every thread may ask);
+//   ScanSums               the tiles' Adler / token / type / kind sums, reduced over a workgroup;
+//   scan_publish           dmx_result, the fallback counters and the launch-shape hint;
+//   zero_stream_tail       zeroes the words past the last block (the framing is ORed there).
+// The apply, once per block:
+//   apply_block            absolute offsets, and zero the words the block shares with a
+//                          neighbour (the pack kernel ORs those); K4's work list.
 // The container header (zlib or gzip), sync flush and trailer are written by the pack kernel
 // (first/last block; put_header, stream_framing).
 struct ScanTile {
@@ -4707,6 +4556,123 @@ struct ScanTile {
     uint64_t kinds;   // K0's block kinds in the tile (16-bit fields: prestored 0, 2, 3, dedupe candidates)
     uint64_t pad_[4];
 };
+__device__ __forceinline__ Mono tile_mono(const ScanTile& T) {   // the tile's aggregate
+    Mono e;
+    e.s = (uint32_t)T.s; e.a = T.a; e.c = T.c;
+    return e;
+}
+// inclusive scan of the lanes' elements, in lane order
+__device__ __forceinline__ Mono mono_wave_scan(Mono x, uint32_t lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const Mono y = mshfl_up(x, o);
+        if (lane >= (uint32_t)o) x = mcompose(y, x);
+    }
+    return x;
+}
+
+// What dmx_result reports beside the layout, summed over tiles: a thread adds its tiles, the
+// wave reduces, lane 0 parks the wave's record in LDS, and after a barrier one thread takes
+// the total.  (The block counts are at most nblk; an Adler sum is below ADL_MOD per thread,
+// so a workgroup's 1 024 of them fit 32 bits.)
+struct ScanSums {
+    uint64_t ntok;
+    uint32_t s1, s2;            // Adler-32's two sums of the input, mod ADL_MOD per add
+    uint32_t nsto, nfix;        // stored and fixed blocks
+    uint32_t k0, k2, k3, ku;    // K0's block kinds (ScanTile::kinds): the launch-shape hint
+    __device__ __forceinline__ void add(const ScanTile& T) {
+        s1 = (s1 + (uint32_t)T.adl_s1) % ADL_MOD;
+        s2 = (s2 + (uint32_t)T.adl_s2) % ADL_MOD;
+        ntok += T.ntok;
+        nsto += (uint32_t)T.nsto;
+        nfix += (uint32_t)T.nfix;
+        k0 += (uint32_t)(T.kinds & 0xFFFFu);
+        k2 += (uint32_t)((T.kinds >> 16) & 0xFFFFu);
+        k3 += (uint32_t)((T.kinds >> 32) & 0xFFFFu);
+        ku += (uint32_t)(T.kinds >> 48);
+    }
+    __device__ __forceinline__ void wave_reduce() {
+        ntok = wave_sum_u64(ntok);
+        s1 = wave_sum_u32(s1); s2 = wave_sum_u32(s2);
+        nsto = wave_sum_u32(nsto); nfix = wave_sum_u32(nfix);
+        k0 = wave_sum_u32(k0); k2 = wave_sum_u32(k2); k3 = wave_sum_u32(k3); ku = wave_sum_u32(ku);
+    }
+    // the workgroup's total from its nw waves' records
+    static __device__ __forceinline__ ScanSums total(const ScanSums* red, uint32_t nw) {
+        ScanSums t = red[0];
+        for (uint32_t w = 1; w < nw; w++) {
+            const ScanSums& r = red[w];
+            t.ntok += r.ntok;
+            t.s1 += r.s1; t.s2 += r.s2;
+            t.nsto += r.nsto; t.nfix += r.nfix;
+            t.k0 += r.k0; t.k2 += r.k2; t.k3 += r.k3; t.ku += r.ku;
+        }
+        return t;
+    }
+};
+
+// Where the stream ends, for `total` = the composed layout of all blocks behind the `start`
+// header bits: T = the end of the last block, end = the byte-aligned end of the DEFLATE data,
+// out_len, and the status -- the only place that decides -E_SZ.
+struct StreamExtent {
+    uint64_t T, end, out_len;
+    int32_t status;
+};
+__device__ __forceinline__ StreamExtent stream_extent(uint32_t flags, uint32_t nblk, uint64_t start, const Mono& total,
+                                                      uint64_t out_cap) {
+    StreamExtent x;
+    x.T = mapply(total, start);
+    if (nblk == 0 && (flags & DMX_F_FINAL) && !(flags & DMX_F_BGZF)) x.T = start + 10;   // empty input: fixed block, EOB only
+    x.end = stream_end(flags, nblk, x.T);
+    x.out_len = x.end / 8 + tail_bits(flags) / 8;
+    x.status = (((x.out_len + 3) & ~3ull) > out_cap) ? -(int32_t)E_SZ : 0;
+    return x;
+}
+
+// One thread, once per encode: the dmx_result record, this encode's sort fallbacks handed to
+// the context's total, and the launch-shape hint of an encode without the work lists
+// (wl_shape).  Returns the stream's check value: Adler-32, or the CRC-32 the CRC launches
+// left (DMX_F_GZIP); DMX_F_BGZF has no stream-wide one: 0.
+__device__ __forceinline__ uint32_t scan_publish(dmx_result* __restrict__ res, uint32_t* __restrict__ nfallback,
+                                                 uint32_t* __restrict__ hint, const uint32_t* __restrict__ crc,
+                                                 uint32_t flags, uint32_t nblk, uint64_t n, const StreamExtent& x,
+                                                 const ScanSums& sums) {
+    const uint64_t a1 = (1 + (uint64_t)sums.s1) % ADL_MOD, a2 = (n % ADL_MOD + sums.s2) % ADL_MOD;
+    const uint32_t check = (flags & DMX_F_BGZF) ? 0u : crc ? crc[0] : (uint32_t)((a2 << 16) | a1);
+    res->out_len = x.out_len;
+    res->end_bits = x.T;
+    res->n = n;
+    res->ntokens = sums.ntok;
+    res->adler = check;
+    res->status = x.status;
+    res->nblocks = nblk;
+    res->nstored = sums.nsto;
+    res->nfixed = sums.nfix;
+    res->ndynamic = nblk - sums.nsto - sums.nfix;
+    res->nsortfallback = nfallback[0];   // this encode's sort fallbacks; zeroed for the next
+    nfallback[1] += nfallback[0];       // and the context's running total
+    res->nsortfallback_total = nfallback[1];
+    nfallback[0] = 0;
+    if (hint) {   // {nblk, |L1|, |L2|, |L4| (the blocks K4 would take), dedupe candidates}
+        __hip_atomic_store(&hint[0], nblk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(&hint[1], sums.k0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(&hint[2], sums.k0 + sums.k2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(&hint[3], nblk - sums.k3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(&hint[4], sums.ku, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    return check;
+}
+
+// Zero the words past the last block, where the framing is ORed in; by nthreads threads.
+__device__ __forceinline__ void zero_stream_tail(uint32_t* __restrict__ out32, uint32_t flags, uint32_t nblk, uint64_t T,
+                                                 uint64_t end, uint32_t tid, uint32_t nthreads) {
+    const uint64_t tail_end = end + tail_bits(flags);
+    // word T >> 5, when the last block ends inside it, is that block's last word: apply_block
+    // zeroes it, keeping any bytes of the whole-copy prefix it holds.  Without a block it is
+    // the first word of the tail.
+    const uint64_t tw0 = nblk ? (T + 31) >> 5 : T >> 5;
+    for (uint64_t w = tw0 + tid; w < ((tail_end + 31) >> 5); w += nthreads) out32[w] = 0;
+}
 
 __device__ __forceinline__ Mono blk_elem(const dmx_blkinfo& bi, uint32_t flags) {
     Mono e = {0, 0, 0};
@@ -4714,6 +4680,49 @@ __device__ __forceinline__ Mono blk_elem(const dmx_blkinfo& bi, uint32_t flags) 
     else if (bi.btype == 0) { e.s = 1; e.a = 3; e.c = 32 + 8 * (uint64_t)bi.n; }
     else { e.c = bi.hdr_bits + bi.body_bits; }
     return e;
+}
+
+// Block b's place in the stream, from its tile's prefix `tp` and the tile-local prefix the
+// tile kernel parked in its record; then the words it shares are zeroed for the pack kernel's
+// ORs, and with the work lists the block goes on K4's list.
+__device__ __forceinline__ void apply_block(dmx_blkinfo* __restrict__ info, uint32_t b, uint32_t nblk, uint32_t flags,
+                                            uint32_t sw, const Mono& tp, uint32_t* __restrict__ out32,
+                                            uint32_t* __restrict__ wl, uint32_t* __restrict__ L4,
+                                            const uint16_t* __restrict__ codes) {
+    const dmx_blkinfo bi = info[b];
+    Mono lp;
+    lp.c = bi.off_bits; lp.s = (uint32_t)(bi.len_bits >> 32); lp.a = bi.len_bits & 0xFFFFFFFFu;
+    const uint64_t o = mapply(mcompose(tp, lp), hdr_bits(flags));
+    const uint64_t l = mapply(blk_elem(bi, flags), o) - o;
+    if (flags & DMX_F_BGZF) {   // o, l: the member; the block record points at its data
+        const uint64_t dl = bgzf_data_bits(bi);
+        info[b].off_bits = o + BGZF_HDR;
+        info[b].len_bits = dl;
+        bgzf_zero_edges(out32, o, l, dl);   // (no whole-copy prefix under the flag: plain zeroing)
+        if (wl && !is_dup(codes, b)) L4[atomicAdd(&wl[WL_N4], 1u)] = b;
+        return;
+    }
+    info[b].off_bits = o;
+    info[b].len_bits = l;
+    if (!wl) {
+        out32[o >> 5] = 0;            // shared with the block before (or the container header: word 0, gzip word 2)
+        out32[(o + l - 1) >> 5] = 0;  // shared with the block after (or the framing)
+        return;
+    }
+    // work lists: a block of the whole-copy prefix has its quads from K0 and gets the rest of
+    // its bytes from K0 too (or the fill kernel: stored_rest, byte stores): nothing to zero;
+    // every other block zeroes its edge words -- only its own bytes where the neighbour is a
+    // whole-copy block (that boundary is a byte boundary: both sides are stored blocks at their
+    // speculative offsets) -- and goes on K4's list
+    const uint32_t M = wl[WL_M];
+    if (wl_skip(b, M, nblk)) return;
+    uint64_t A, P;
+    wl_prefix_bytes(M, nblk, sw, flags, A, P);
+    const uint64_t w0 = o >> 5, w1 = (o + l - 1) >> 5;
+    zero_word_keep(out32, w0, A, P);
+    if (w1 != w0) zero_word_keep(out32, w1, A, P);
+    if (is_dup(codes, b)) return;   // packed by dmx_dup_copy_kernel
+    L4[atomicAdd(&wl[WL_N4], 1u)] = b;
 }
 
 __global__ __launch_bounds__(SCAN_TILE) void dmx_scan_tile_kernel(dmx_blkinfo* __restrict__ info, uint32_t nblk,
@@ -4756,12 +4765,7 @@ __global__ __launch_bounds__(SCAN_TILE) void dmx_scan_tile_kernel(dmx_blkinfo* _
         ns = bi.btype == 0;
         nf = bi.btype == 1;
     }
-    Mono x = e;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const Mono y = mshfl_up(x, o);
-        if (lane >= (uint32_t)o) x = mcompose(y, x);
-    }
+    const Mono x = mono_wave_scan(e, lane);
     const Mono before = mshfl_up(x, 1);
     if (lane == 63) wtot[wave] = x;
     s1 = wave_sum_u64(s1);
@@ -4775,7 +4779,7 @@ __global__ __launch_bounds__(SCAN_TILE) void dmx_scan_tile_kernel(dmx_blkinfo* _
     Mono pre = {0, 0, 0};
     for (uint32_t w = 0; w < wave; w++) pre = mcompose(pre, wtot[w]);
     if (lane) pre = mcompose(pre, before);
-    if (b < nblk) {   // tile-local exclusive prefix, finished by dmx_scan_apply_kernel
+    if (b < nblk) {   // tile-local exclusive prefix, finished by apply_block
         info[b].off_bits = pre.c;
         info[b].len_bits = ((uint64_t)pre.s << 32) | pre.a;
     }
@@ -4798,48 +4802,26 @@ __global__ __launch_bounds__(ST) void dmx_scan_kernel(ScanTile* __restrict__ til
                                                       uint32_t* __restrict__ nfallback, uint32_t* __restrict__ hint,
                                                       const uint32_t* __restrict__ crc) {
     __shared__ Mono wtot[ST / 64];
-    __shared__ uint32_t kcnt[4];
     __shared__ Mono carry_s;
-    __shared__ uint64_t red[ST / 64][5];
+    __shared__ ScanSums red[ST / 64];
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint64_t start = hdr_bits(flags);
     const uint32_t ntile = (nblk + SCAN_TILE - 1) / SCAN_TILE;
-    uint64_t adl_s1 = 0, adl_s2 = 0, ntok = 0, nsto = 0, nfix = 0;
-    uint32_t k0 = 0, k2 = 0, k3 = 0, ku = 0;
-    if (tid < 4) kcnt[tid] = 0;
     // thread t owns tiles [t C, t C + C)
     const uint32_t C = (ntile + ST - 1) / ST;
     const uint32_t t0 = tid * C < ntile ? tid * C : ntile, t1 = t0 + C < ntile ? t0 + C : ntile;
     Mono agg = {0, 0, 0};
+    ScanSums sums = {};
     for (uint32_t t = t0; t < t1; t++) {
         const ScanTile T = tiles[t];
-        Mono e;
-        e.s = (uint32_t)T.s; e.a = T.a; e.c = T.c;
-        agg = mcompose(agg, e);
-        adl_s1 = (adl_s1 + T.adl_s1) % ADL_MOD;
-        adl_s2 = (adl_s2 + T.adl_s2) % ADL_MOD;
-        ntok += T.ntok;
-        nsto += T.nsto;
-        nfix += T.nfix;
-        k0 += (uint32_t)(T.kinds & 0xFFFFu);
-        k2 += (uint32_t)((T.kinds >> 16) & 0xFFFFu);
-        k3 += (uint32_t)((T.kinds >> 32) & 0xFFFFu);
-        ku += (uint32_t)(T.kinds >> 48);
+        agg = mcompose(agg, tile_mono(T));
+        sums.add(T);
     }
-    Mono x = agg;  // inclusive scan in the wave
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const Mono y = mshfl_up(x, o);
-        if (lane >= (uint32_t)o) x = mcompose(y, x);
-    }
+    const Mono x = mono_wave_scan(agg, lane);
     if (lane == 63) wtot[wave] = x;
-    __syncthreads();   // (kcnt zeroed)
-    if (hint) {   // the launch-shape hint of an encode without the work lists (wl_shape)
-        if (k0) atomicAdd(&kcnt[0], k0);
-        if (k2) atomicAdd(&kcnt[1], k2);
-        if (k3) atomicAdd(&kcnt[2], k3);
-        if (ku) atomicAdd(&kcnt[3], ku);
-    }
+    sums.wave_reduce();
+    if (lane == 0) red[wave] = sums;
+    __syncthreads();
     if (tid == 0) {   // exclusive prefix over waves
         Mono acc = {0, 0, 0};
         for (int w = 0; w < ST / 64; w++) {
@@ -4855,75 +4837,18 @@ __global__ __launch_bounds__(ST) void dmx_scan_kernel(ScanTile* __restrict__ til
         Mono pre = (lane == 0) ? wtot[wave] : mcompose(wtot[wave], before);
         for (uint32_t t = t0; t < t1; t++) {
             tiles[t].ps = pre.s; tiles[t].pa = pre.a; tiles[t].pc = pre.c;
-            Mono e;
-            e.s = (uint32_t)tiles[t].s; e.a = tiles[t].a; e.c = tiles[t].c;
-            pre = mcompose(pre, e);
+            pre = mcompose(pre, tile_mono(tiles[t]));
         }
     }
-    // reductions
-    adl_s1 = wave_sum_u64(adl_s1 % ADL_MOD);
-    adl_s2 = wave_sum_u64(adl_s2 % ADL_MOD);
-    ntok = wave_sum_u64(ntok);
-    nsto = wave_sum_u64(nsto);
-    nfix = wave_sum_u64(nfix);
-    if (lane == 0) { red[wave][0] = adl_s1; red[wave][1] = adl_s2; red[wave][2] = ntok; red[wave][3] = nsto; red[wave][4] = nfix; }
-    __syncthreads();
-    __shared__ uint64_t s_end, s_T;
-    __shared__ uint32_t s_adler;
-    __shared__ int32_t s_status;
-    if (tid == 0) {
-        uint64_t s1 = 0, s2 = 0, nt = 0, ns = 0, nf = 0;
-        for (int w = 0; w < ST / 64; w++) { s1 += red[w][0]; s2 += red[w][1]; nt += red[w][2]; ns += red[w][3]; nf += red[w][4]; }
-        s1 = (1 + s1) % ADL_MOD;
-        s2 = (n % ADL_MOD + s2) % ADL_MOD;
-        // the stream's check value: Adler-32, or the CRC-32 the CRC launches left (DMX_F_GZIP)
-        // (DMX_F_BGZF has no stream-wide one: 0)
-        const uint32_t adler = (flags & DMX_F_BGZF) ? 0u : crc ? crc[0] : (uint32_t)((s2 << 16) | s1);
-        uint64_t T = mapply(carry_s, start);
-        if (nblk == 0 && (flags & DMX_F_FINAL) && !(flags & DMX_F_BGZF)) T = start + 10;   // empty input: fixed block, EOB only
-        uint64_t end = stream_end(flags, nblk, T);
-        uint64_t out_len = end / 8 + tail_bits(flags) / 8;
-        int32_t status = 0;
-        if (((out_len + 3) & ~3ull) > out_cap) status = -(int32_t)E_SZ;
-        res->out_len = out_len;
-        res->end_bits = T;
-        res->n = n;
-        res->ntokens = nt;
-        res->adler = adler;
-        res->status = status;
-        res->nblocks = nblk;
-        res->nstored = (uint32_t)ns;
-        res->nfixed = (uint32_t)nf;
-        res->ndynamic = nblk - (uint32_t)ns - (uint32_t)nf;
-        res->nsortfallback = nfallback[0];   // this encode's sort fallbacks; zeroed for the next
-        nfallback[1] += nfallback[0];       // and the context's running total
-        res->nsortfallback_total = nfallback[1];
-        nfallback[0] = 0;
-        if (hint) {   // {nblk, |L1|, |L2|, |L4| (the blocks K4 would take), dedupe candidates}
-            __hip_atomic_store(&hint[0], nblk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(&hint[1], kcnt[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(&hint[2], kcnt[0] + kcnt[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(&hint[3], nblk - kcnt[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(&hint[4], kcnt[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-        s_end = end;
-        s_T = T;
-        s_adler = adler;
-        s_status = status;
-    }
-    __syncthreads();
-    if (s_status) return;
-    // zero the words past the last block (the framing goes there)
-    const uint64_t T = s_T, end = s_end;
-    const uint64_t tail_end = end + tail_bits(flags);
-    // (word T >> 5, when the last block ends inside it, is that block's last word: the apply
-    // launch zeroes it, keeping any bytes of the whole-copy prefix it holds)
-    const uint64_t tw0 = nblk ? (T + 31) >> 5 : T >> 5;
-    for (uint64_t w = tw0 + tid; w < ((tail_end + 31) >> 5); w += ST) out32[w] = 0;
+    const StreamExtent ext = stream_extent(flags, nblk, start, carry_s, out_cap);
+    uint32_t check = 0;
+    if (tid == 0) check = scan_publish(res, nfallback, hint, crc, flags, nblk, n, ext, ScanSums::total(red, ST / 64));
+    if (ext.status) return;
+    zero_stream_tail(out32, flags, nblk, ext.T, ext.end, tid, ST);
     if (nblk == 0) {   // no pack launch: the whole stream is written here
         if (tid <= (start >> 5) && start) out32[tid] = 0;   // every word the header touches (T >> 5 is at or past the last)
         __syncthreads();
-        if (tid == 0) stream_framing(out32, flags, 0, T, end, s_adler, n);
+        if (tid == 0) stream_framing(out32, flags, 0, ext.T, ext.end, check, n);
     }
 }
 
@@ -4936,52 +4861,18 @@ __global__ __launch_bounds__(SCAN_TILE) void dmx_scan_apply_kernel(dmx_blkinfo* 
     if (res->status) return;
     const uint32_t b = blockIdx.x * SCAN_TILE + threadIdx.x;
     if (b >= nblk) return;
-    const uint64_t start = hdr_bits(flags);
     const ScanTile& T = tiles[blockIdx.x];
-    Mono tp, lp;
+    Mono tp;   // the prefix dmx_scan_kernel left
     tp.s = (uint32_t)T.ps; tp.a = T.pa; tp.c = T.pc;
-    const dmx_blkinfo bi = info[b];
-    lp.c = bi.off_bits; lp.s = (uint32_t)(bi.len_bits >> 32); lp.a = bi.len_bits & 0xFFFFFFFFu;
-    const Mono pre = mcompose(tp, lp);
-    const uint64_t o = mapply(pre, start);
-    const uint64_t l = mapply(blk_elem(bi, flags), o) - o;
-    if (flags & DMX_F_BGZF) {   // o, l: the member; the block record points at its data
-        const uint64_t dl = bgzf_data_bits(bi);
-        info[b].off_bits = o + BGZF_HDR;
-        info[b].len_bits = dl;
-        bgzf_zero_edges(out32, o, l, dl);   // (no whole-copy prefix under the flag: plain zeroing)
-        if (wl && !is_dup(codes, b)) L4[atomicAdd(&wl[WL_N4], 1u)] = b;
-        return;
-    }
-    info[b].off_bits = o;
-    info[b].len_bits = l;
-    if (!wl) {
-        out32[o >> 5] = 0;            // shared with the block before (or the container header: word 0, gzip word 2)
-        out32[(o + l - 1) >> 5] = 0;  // shared with the block after (or the framing)
-        return;
-    }
-    // work lists: a block of the whole-copy prefix has its quads from K0 and gets the rest of
-    // its bytes from K0 too (or the fill kernel: stored_rest, byte stores): nothing to zero; every other block zeroes its edge words -- only its own bytes where the neighbour is a
-    // whole-copy block (that boundary is a byte boundary: both sides are stored blocks at their
-    // speculative offsets) -- and goes on K4's list
-    const uint32_t M = wl[WL_M];
-    if (wl_skip(b, M, nblk)) return;
-    uint64_t A, P;
-    wl_prefix_bytes(M, nblk, sw, flags, A, P);
-    const uint64_t w0 = o >> 5, w1 = (o + l - 1) >> 5;
-    zero_word_keep(out32, w0, A, P);
-    if (w1 != w0) zero_word_keep(out32, w1, A, P);
-    if (is_dup(codes, b)) return;   // packed by dmx_dup_copy_kernel
-    L4[atomicAdd(&wl[WL_N4], 1u)] = b;
+    apply_block(info, b, nblk, flags, sw, tp, out32, wl, L4, codes);
 }
 
-// K3 in two launches when the stream has at most SA1_MAXT tiles (8 GiB of 32 KiB blocks):
-// dmx_scan_tile_kernel as above, then this kernel, a workgroup per tile, which composes the
-// tile aggregates itself (at most 4 per thread) -- its tile's prefix and the stream's total,
-// hence the status every workgroup needs before it writes -- instead of a one-workgroup
-// dmx_scan_kernel launch between the two.  The last tile's workgroup also does what that
-// launch did once: Adler-32, the dmx_result record, the fallback counters, the hint and the
-// words past the last block.  Then each block: as dmx_scan_apply_kernel.
+// K3's second launch when the stream has at most SA1_MAXT tiles (8 GiB of 32 KiB blocks): a
+// workgroup per tile, which composes the tile aggregates itself (at most 4 per thread) -- its
+// tile's prefix and the stream's total, hence the status every workgroup needs before it
+// writes -- instead of a one-workgroup dmx_scan_kernel launch before the apply.  The last
+// tile's workgroup finishes the layout (only it sums the tiles' records); then every block is
+// applied.
 #define SA1_MAXT (4 * SCAN_TILE)
 __global__ __launch_bounds__(SCAN_TILE) void dmx_scan_apply1_kernel(dmx_blkinfo* __restrict__ info, uint32_t nblk, uint64_t n,
                                                                    uint32_t flags, uint64_t out_cap, uint32_t sw,
@@ -4993,46 +4884,28 @@ __global__ __launch_bounds__(SCAN_TILE) void dmx_scan_apply1_kernel(dmx_blkinfo*
                                                                    const uint32_t* __restrict__ crc) {
     __shared__ Mono wt[SCAN_TILE / 64];
     __shared__ Mono s_pre;
-    __shared__ uint64_t red[SCAN_TILE / 64][9];
+    __shared__ ScanSums red[SCAN_TILE / 64];
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t ntile = (nblk + SCAN_TILE - 1) / SCAN_TILE, tt = blockIdx.x;
     const bool lastwg = tt + 1 == ntile;
-    const uint64_t start = hdr_bits(flags);
     // thread i composes tiles [i C, i C + C) in order; the one holding tile tt notes the part before it
     const uint32_t C = (ntile + SCAN_TILE - 1) / SCAN_TILE;
     const uint32_t t0 = tid * C < ntile ? tid * C : ntile, t1 = t0 + C < ntile ? t0 + C : ntile;
     Mono agg = {0, 0, 0}, part = {0, 0, 0};
     bool mine = false;
-    uint64_t s1 = 0, s2 = 0, nt = 0, ns = 0, nf = 0, k0 = 0, k2 = 0, k3 = 0, ku = 0;
+    ScanSums sums = {};
     for (uint32_t u = t0; u < t1; u++) {
         const ScanTile T = tiles[u];
         if (u == tt) { part = agg; mine = true; }
-        Mono e;
-        e.s = (uint32_t)T.s; e.a = T.a; e.c = T.c;
-        agg = mcompose(agg, e);
-        if (lastwg) {
-            s1 = (s1 + T.adl_s1) % ADL_MOD;
-            s2 = (s2 + T.adl_s2) % ADL_MOD;
-            nt += T.ntok; ns += T.nsto; nf += T.nfix;
-            k0 += T.kinds & 0xFFFFu; k2 += (T.kinds >> 16) & 0xFFFFu; k3 += (T.kinds >> 32) & 0xFFFFu; ku += T.kinds >> 48;
-        }
+        agg = mcompose(agg, tile_mono(T));
+        if (lastwg) sums.add(T);
     }
-    Mono x = agg;   // inclusive scan over the threads' ranges
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const Mono y = mshfl_up(x, o);
-        if (lane >= (uint32_t)o) x = mcompose(y, x);
-    }
+    const Mono x = mono_wave_scan(agg, lane);   // over the threads' ranges
     const Mono before = mshfl_up(x, 1);
     if (lane == 63) wt[wave] = x;
     if (lastwg) {
-        s1 = wave_sum_u64(s1); s2 = wave_sum_u64(s2); nt = wave_sum_u64(nt);
-        ns = wave_sum_u64(ns); nf = wave_sum_u64(nf);
-        k0 = wave_sum_u64(k0); k2 = wave_sum_u64(k2); k3 = wave_sum_u64(k3); ku = wave_sum_u64(ku);
-        if (lane == 0) {
-            red[wave][0] = s1; red[wave][1] = s2; red[wave][2] = nt; red[wave][3] = ns; red[wave][4] = nf;
-            red[wave][5] = k0; red[wave][6] = k2; red[wave][7] = k3; red[wave][8] = ku;
-        }
+        sums.wave_reduce();
+        if (lane == 0) red[wave] = sums;
     }
     __syncthreads();
     Mono tot = {0, 0, 0}, wpre = {0, 0, 0};
@@ -5043,79 +4916,14 @@ __global__ __launch_bounds__(SCAN_TILE) void dmx_scan_apply1_kernel(dmx_blkinfo*
     }
     if (mine) s_pre = mcompose(lane ? mcompose(wpre, before) : wpre, part);
     // the stream's end and status (every workgroup: nothing is written past out_cap)
-    const uint64_t T = mapply(tot, start);
-    const uint64_t end = stream_end(flags, nblk, T);
-    const uint64_t out_len = end / 8 + tail_bits(flags) / 8;
-    const int32_t status = (((out_len + 3) & ~3ull) > out_cap) ? -(int32_t)E_SZ : 0;
-    if (lastwg && tid == 0) {
-        uint64_t a1 = 0, a2 = 0, ntk = 0, nst = 0, nfx = 0, q0 = 0, q2 = 0, q3 = 0, qu = 0;
-        for (int w = 0; w < SCAN_TILE / 64; w++) {
-            a1 += red[w][0]; a2 += red[w][1]; ntk += red[w][2]; nst += red[w][3]; nfx += red[w][4];
-            q0 += red[w][5]; q2 += red[w][6]; q3 += red[w][7]; qu += red[w][8];
-        }
-        a1 = (1 + a1) % ADL_MOD;
-        a2 = (n % ADL_MOD + a2) % ADL_MOD;
-        res->out_len = out_len;
-        res->end_bits = T;
-        res->n = n;
-        res->ntokens = ntk;
-        res->adler = (flags & DMX_F_BGZF) ? 0u : crc ? crc[0] : (uint32_t)((a2 << 16) | a1);   // (as dmx_scan_kernel)
-        res->status = status;
-        res->nblocks = nblk;
-        res->nstored = (uint32_t)nst;
-        res->nfixed = (uint32_t)nfx;
-        res->ndynamic = nblk - (uint32_t)nst - (uint32_t)nfx;
-        res->nsortfallback = nfallback[0];
-        nfallback[1] += nfallback[0];
-        res->nsortfallback_total = nfallback[1];
-        nfallback[0] = 0;
-        if (hint) {   // as dmx_scan_kernel
-            __hip_atomic_store(&hint[0], nblk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(&hint[1], (uint32_t)q0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(&hint[2], (uint32_t)(q0 + q2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(&hint[3], nblk - (uint32_t)q3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(&hint[4], (uint32_t)qu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
-    if (status) return;
-    if (lastwg) {   // zero the words past the last block (the framing goes there)
-        const uint64_t tail_end = end + tail_bits(flags);
-        for (uint64_t w = ((T + 31) >> 5) + tid; w < ((tail_end + 31) >> 5); w += SCAN_TILE) out32[w] = 0;   // (as dmx_scan_kernel)
-    }
+    const StreamExtent ext = stream_extent(flags, nblk, hdr_bits(flags), tot, out_cap);
+    if (lastwg && tid == 0)
+        scan_publish(res, nfallback, hint, crc, flags, nblk, n, ext, ScanSums::total(red, SCAN_TILE / 64));
+    if (ext.status) return;
+    if (lastwg) zero_stream_tail(out32, flags, nblk, ext.T, ext.end, tid, SCAN_TILE);
     __syncthreads();   // (s_pre)
     const uint32_t b = tt * SCAN_TILE + tid;
-    if (b >= nblk) return;
-    const Mono tp = s_pre;
-    Mono lp;
-    const dmx_blkinfo bi = info[b];
-    lp.c = bi.off_bits; lp.s = (uint32_t)(bi.len_bits >> 32); lp.a = bi.len_bits & 0xFFFFFFFFu;
-    const Mono pre = mcompose(tp, lp);
-    const uint64_t o = mapply(pre, start);
-    const uint64_t l = mapply(blk_elem(bi, flags), o) - o;
-    if (flags & DMX_F_BGZF) {   // (as dmx_scan_apply_kernel)
-        const uint64_t dl = bgzf_data_bits(bi);
-        info[b].off_bits = o + BGZF_HDR;
-        info[b].len_bits = dl;
-        bgzf_zero_edges(out32, o, l, dl);
-        if (wl && !is_dup(codes, b)) L4[atomicAdd(&wl[WL_N4], 1u)] = b;
-        return;
-    }
-    info[b].off_bits = o;
-    info[b].len_bits = l;
-    if (!wl) {
-        out32[o >> 5] = 0;
-        out32[(o + l - 1) >> 5] = 0;
-        return;
-    }
-    const uint32_t M = wl[WL_M];
-    if (wl_skip(b, M, nblk)) return;
-    uint64_t A, P;
-    wl_prefix_bytes(M, nblk, sw, flags, A, P);
-    const uint64_t w0 = o >> 5, w1 = (o + l - 1) >> 5;
-    zero_word_keep(out32, w0, A, P);
-    if (w1 != w0) zero_word_keep(out32, w1, A, P);
-    if (is_dup(codes, b)) return;
-    L4[atomicAdd(&wl[WL_N4], 1u)] = b;
+    if (b < nblk) apply_block(info, b, nblk, flags, sw, s_pre, out32, wl, L4, codes);
 }
 
 // ------------------------------------------------------------------------------------
@@ -5167,12 +4975,10 @@ __device__ __forceinline__ void pack_one(const uint32_t b, const uint8_t* __rest
                                          dmx_result* __restrict__ res, const uint32_t* __restrict__ bcrc) {
     __shared__ uint32_t stage[PK_RING];
     __shared__ uint32_t code[DMX_HIST];
-#ifndef DMX_PACK_OLD
     // one entry per first piece of a token, value | bits << 24: literals 0..255, then the
     // lengths 3..258 with their extra bits appended (the length symbol, its code and its extra
     // bits in one read instead of len_sym arithmetic and a branch per token)
     __shared__ uint32_t ptab[512];
-#endif
     __shared__ uint32_t wsum[PT / 64];
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const dmx_blkinfo bi = info[b];   // in flight with the status load (a stored block's WG is
@@ -5180,7 +4986,7 @@ __device__ __forceinline__ void pack_one(const uint32_t b, const uint8_t* __rest
     const uint64_t O = bi.off_bits, Lb = bi.len_bits;
     const uint32_t s0 = (uint32_t)(O & 31);
     const uint32_t nwords = (uint32_t)((s0 + Lb + 31) >> 5);
-    const uint32_t final_bit = (((flags & DMX_F_FINAL) && b == nblk - 1) || (flags & DMX_F_BGZF)) ? 1u : 0u;
+    const uint32_t final_bit = block_is_final(flags, b, nblk);
     // DMX_F_BGZF: the member's header and trailer around the data (bcrc: the blocks' CRC-32s).  The
     // data's first and last words are then shared with those, not with a neighbour: same atomicOr.
     if (tid == 0 && (flags & DMX_F_BGZF)) bgzf_member_framing(out32, O, Lb, bcrc[b], bi.n);
@@ -5287,7 +5093,6 @@ __device__ __forceinline__ void pack_one(const uint32_t b, const uint8_t* __rest
     for (uint32_t k = tid; k < PK_RING; k += PT) stage[k] = 0;
     for (uint32_t k = tid; k < 316; k += PT) code[k] = codes_g[(uint64_t)b * DMX_NSUB * DMX_HIST + k];
     __syncthreads();
-#ifndef DMX_PACK_OLD
     auto build_ptab = [&]() {   // (after code[] is complete; a barrier follows)
         for (uint32_t k = tid; k < 512; k += PT) {
             uint32_t e;
@@ -5305,7 +5110,6 @@ __device__ __forceinline__ void pack_one(const uint32_t b, const uint8_t* __rest
     };
     build_ptab();
     __syncthreads();
-#endif
     {   // (stored blocks left above)
         // one or more DEFLATE blocks (f3 split): header, tokens [t0, t1), end of block
         uint32_t pos = s0;   // block bit position
@@ -5318,10 +5122,8 @@ __device__ __forceinline__ void pack_one(const uint32_t b, const uint8_t* __rest
 #pragma unroll
                 for (int t = 0; t < TPT; t++) nxt[t] = tb[min(si.t0 + tid * TPT + (uint32_t)t, (uint32_t)DMX_BLK - 1)];
                 __syncthreads();
-#ifndef DMX_PACK_OLD
                 build_ptab();
                 __syncthreads();
-#endif
             }
             flush(pos);
             const uint32_t* hg = hdr_g + slot * DMX_HDR_WORDS;
@@ -5349,7 +5151,6 @@ __device__ __forceinline__ void pack_one(const uint32_t b, const uint8_t* __rest
                 uint32_t mybits = 0;
     #pragma unroll
                 for (int t = 0; t < TPT; t++) {
-#ifndef DMX_PACK_OLD
                     {   // both pieces without a branch: the first from ptab, the distance's computed
                         // for every token and dropped for a literal; slots past the sub-block's
                         // last token (the last round) get no bits
@@ -5370,28 +5171,6 @@ __device__ __forceinline__ void pack_one(const uint32_t b, const uint8_t* __rest
                         pb[2 * t + 1] = dd ? (cw >> 16) + eb : 0u;
                         mybits += pb[2 * t] + pb[2 * t + 1];
                     }
-#else
-                    pv[2 * t] = pb[2 * t] = pv[2 * t + 1] = pb[2 * t + 1] = 0;
-                    if (j0 + t < si.t1) {
-                        const uint32_t tk = cur[t];
-                        if ((tk >> 9) == 0) {
-                            const uint32_t cw = code[tk];
-                            pv[2 * t] = cw & 0xFFFFu;
-                            pb[2 * t] = cw >> 16;
-                        } else {
-                            uint32_t sy, eb, ev;
-                            len_sym(tk & 0x1FFu, sy, eb, ev);
-                            uint32_t cw = code[sy];
-                            pv[2 * t] = (cw & 0xFFFFu) | (ev << (cw >> 16));
-                            pb[2 * t] = (cw >> 16) + eb;
-                            dist_sym(tk >> 9, sy, eb, ev);
-                            cw = code[DMX_DIST0 + sy];
-                            pv[2 * t + 1] = (cw & 0xFFFFu) | (ev << (cw >> 16));
-                            pb[2 * t + 1] = (cw >> 16) + eb;
-                        }
-                        mybits += pb[2 * t] + pb[2 * t + 1];
-                    }
-#endif
                 }
                 // exclusive scan of the threads' bit counts over the workgroup
                 const uint32_t incl = wave_incl_scan(mybits);
