@@ -143,6 +143,31 @@ __device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
     v += dpp_shr64(v, 8);
     return readlane64(v, 15) + readlane64(v, 31) + readlane64(v, 47) + readlane64(v, 63);
 }
+// The same for 32-bit values whose sums over a row of 16 lanes fit in 32 bits but whose wave
+// sum may not: the rows add up in the vector registers, the four row sums as 64-bit scalars.
+__device__ __forceinline__ uint64_t wave_sum_u32_wide(uint32_t v) {
+    v += DMX_DPP_SHR(v, 1);
+    v += DMX_DPP_SHR(v, 2);
+    v += DMX_DPP_SHR(v, 4);
+    v += DMX_DPP_SHR(v, 8);
+    return (uint64_t)(uint32_t)__builtin_amdgcn_readlane(v, 15) + (uint32_t)__builtin_amdgcn_readlane(v, 31) +
+           (uint32_t)__builtin_amdgcn_readlane(v, 47) + (uint32_t)__builtin_amdgcn_readlane(v, 63);
+}
+// a - b in each 16-bit half (v_pk_sub_u16)
+typedef uint16_t dmx_u16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t pk_sub_u16(uint32_t a, uint32_t b) {
+    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(dmx_u16x2, a) - __builtin_bit_cast(dmx_u16x2, b));
+}
+// Adler-32 partial sums of 16 bytes held as four words (byte j of the 16 in word j / 4):
+// ts += the sum of the bytes, tt += the sum of j * byte j.  Two instructions per word
+// (v_sad_u8, v_dot4_u32_u8); K0's pass 1 and K1's staging loop share it.
+__device__ __forceinline__ void adler16(const uint32_t* w, uint32_t& ts, uint32_t& tt) {
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        ts = __builtin_amdgcn_sad_u8(w[q], 0u, ts);
+        tt = __builtin_amdgcn_udot4(w[q], 0x03020100u + 0x04040404u * q, tt, false);
+    }
+}
 
 // ------------------------------------------------------------------------------------
 // K1: bucket-sorted chains + longest match of every position + greedy path + compaction
@@ -1401,6 +1426,20 @@ __device__ __forceinline__ uint32_t atomic_rank16(uint32_t* T, uint32_t v, bool 
     return (atomicAdd(&T[v], valid ? 1u << sh : 0u) >> sh) & 0xFFFFu;
 }
 
+// DMX_F_DEEP (block_chain below; dmx_oracle_block_chain): the deep chain depth of this
+// launch, and the number of sampled positions (p < nvalid with p mod 2048 < 256)
+__device__ __forceinline__ int32_t deep_chain_of(uint32_t mflags) {
+    return (mflags >> 16) & 0xFFu ? (int32_t)((mflags >> 16) & 0xFFu) : (int32_t)DMX_DEEP_CHAIN;
+}
+__device__ __forceinline__ uint32_t deep_samples(uint32_t nvalid) {
+    uint32_t ns = 0;
+    for (uint32_t s = 0; s < 16; s++) {
+        const uint32_t lo = s << 11;
+        ns += nvalid > lo ? min(nvalid - lo, 256u) : 0u;
+    }
+    return ns;
+}
+
 // Bucket-sorted positions S (stable by position inside a bucket) by ONE counting pass over
 // the 13-bit bucket (round 5; the two-pass LSD sort below stays as the checked fallback).
 // The block's positions form four groups of 8192 (g = w >> 2 for wave w; round 6: two groups
@@ -1422,9 +1461,17 @@ __device__ __forceinline__ uint32_t atomic_rank16(uint32_t* T, uint32_t v, bool 
 // One rank atomic per entry instead of the LSD sort's two (plus its second count), and the
 // scatter is plain stores.  The search checks every adjacent pair of S (sortbad), so a lane
 // order violation can never go unnoticed: the block then re-sorts with the match-any path.
-template <bool RUNCHK, int NB>
-__device__ __forceinline__ void count_sort_positions(MatchLDS& L, uint32_t bn, int32_t max_chain, uint32_t tid,
-                                                     bool stamp, uint64_t* tp0) {
+// DEEP with deep_dk > 0 (the trigram sort of a DMX_F_DEEP launch whose two depths are both
+// at most KD, match_block): the block's chain depth by block_chain's rule, from this sort's
+// own hashes.  Block_chain's samples, p mod 2048 < 256, are steps 0..3 of every wave
+// (x = 2048 w + lane + 64 st), so their buckets are hh[0] and hh[1]: they go into the
+// 8192-bit set in L.hist (zero until P3) before the first ranking round, four waves that do
+// not rank in the second round count the set, zero it again and add into L.ntok (zero until
+// the search), and the sum is read after the rounds.  Returns the depth (else max_chain).
+template <bool RUNCHK, int NB, bool DEEP>
+__device__ __forceinline__ int32_t count_sort_positions(MatchLDS& L, uint32_t bn, int32_t max_chain, uint32_t tid,
+                                                        bool stamp, uint64_t* tp0, int32_t deep_dk) {
+    static_assert(!DEEP || NB == 3, "the depth statistic hashes trigrams");
     const uint32_t lane = tid & 63, wave = wave_of(tid);
     const uint32_t nvalid = bn > 2 ? bn - 2 : 0;   // positions with a full trigram
     const bool need_starts = max_chain <= 0 || max_chain > KD;
@@ -1453,11 +1500,27 @@ __device__ __forceinline__ void count_sort_positions(MatchLDS& L, uint32_t bn, i
         hh[st >> 1] = ha | (hb << 16);
         if ((st & 7) == 6) __builtin_amdgcn_sched_barrier(0);   // 8 loads in flight per group
     }
+    const bool deep = DEEP && deep_dk > 0;
+    if (deep) {   // the sampled positions' buckets into the bit set
+#pragma unroll
+        for (int st = 0; st < 4; st++) {
+            const uint32_t h = (hh[st >> 1] >> (16 * (st & 1))) & 0xFFFFu;
+            if (x0l + ((uint32_t)st << 6) < nvl) atomicOr(&L.hist[h >> 5], 1u << (h & 31));
+        }
+    }
     if (stamp && tid == 0) tp0[0] = __builtin_amdgcn_s_memtime();
     uint32_t rk[16];                        // rank of each entry, two per register
 #pragma unroll
     for (int j = 0; j < 16; j++) rk[j] = 0;
     for (uint32_t r = 0; r < NR; r++) {
+        // the set is complete after the first round's barrier: waves 0, 2, 4 and 6 (which rank
+        // in rounds 0 and 2) count 64 of its 256 words each
+        if (deep && r == 1 && wave < 8 && !(wave & 1)) {
+            const uint32_t k = (wave << 5) + lane;
+            const uint32_t c = wave_sum_u32((uint32_t)__popc(L.hist[k]));
+            L.hist[k] = 0;
+            if (lane == 0) atomicAdd(&L.ntok, c);
+        }
         if (r == (wave & (NR - 1))) {
             asm volatile("" : "+v"(x0l), "+v"(nvl));
             if (RUNCHK) {
@@ -1492,6 +1555,8 @@ __device__ __forceinline__ void count_sort_positions(MatchLDS& L, uint32_t bn, i
         __syncthreads();
     }
     if (stamp && tid == 0) tp0[1] = __builtin_amdgcn_s_memtime();
+    // (L.ntok is complete since the second round's barrier; the search zeroes it again)
+    const int32_t kb = deep && 4 * L.ntok < deep_samples(nvalid) ? deep_dk : max_chain;
     {   // bucket starts: thread t scans buckets 8t .. 8t + 7
         const uint4 a = reinterpret_cast<const uint4*>(T)[2 * tid], c = reinterpret_cast<const uint4*>(T)[2 * tid + 1];
         uint32_t w[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w}, pre[8], s = 0;
@@ -1539,6 +1604,7 @@ __device__ __forceinline__ void count_sort_positions(MatchLDS& L, uint32_t bn, i
     }
     __syncthreads();
     if (stamp && tid == 0) tp0[2] = __builtin_amdgcn_s_memtime();
+    return kb;
 }
 
 // Bucket-sorted positions S (stable by position inside a bucket), built here instead of
@@ -1560,13 +1626,12 @@ __device__ __forceinline__ void count_sort_positions(MatchLDS& L, uint32_t bn, i
 // RUNCHK: count_add / atomic_rank first test whether all lanes of a step share one digit
 // (runs), which turns a 64-way same-address atomic into one add; blocks that are not
 // run-dominated (counted while staging) skip that test (correct either way).
-template <bool EXACT, bool RUNCHK = true, int NB = 3>
-__device__ __forceinline__ void sort_positions(MatchLDS& L, uint32_t bn, int32_t max_chain, uint32_t tid, bool stamp,
-                                               uint64_t* tp0) {
-    if constexpr (!EXACT) {
-        count_sort_positions<RUNCHK, NB>(L, bn, max_chain, tid, stamp, tp0);
-        return;
-    }
+// Returns the block's chain depth: max_chain, or the counting sort's verdict (DEEP, deep_dk).
+template <bool EXACT, bool RUNCHK = true, int NB = 3, bool DEEP = false>
+__device__ __forceinline__ int32_t sort_positions(MatchLDS& L, uint32_t bn, int32_t max_chain, uint32_t tid, bool stamp,
+                                                  uint64_t* tp0, int32_t deep_dk = 0) {
+    static_assert(!(EXACT && DEEP), "only the counting sort takes the depth statistic along");
+    if constexpr (!EXACT) return count_sort_positions<RUNCHK, NB, DEEP>(L, bn, max_chain, tid, stamp, tp0, deep_dk);
     const uint32_t lane = tid & 63, wave = wave_of(tid);
     const uint32_t nvalid = bn > 2 ? bn - 2 : 0;   // positions with a full trigram
     const bool need_starts = max_chain <= 0 || max_chain > KD;
@@ -1692,6 +1757,7 @@ __device__ __forceinline__ void sort_positions(MatchLDS& L, uint32_t bn, int32_t
     }
     __syncthreads();
     if (stamp && tid == 0) tp0[2] = __builtin_amdgcn_s_memtime();
+    return max_chain;
 }
 
 
@@ -2444,11 +2510,7 @@ __device__ __forceinline__ uint32_t store_check_block(const uint8_t* __restrict_
     uint64_t s = 0, t = 0;
     auto chunk1 = [&](uint32_t p, const uint32_t* w) {   // 16 bytes at block offset p
         uint32_t ts = 0, tt = 0;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            ts = __builtin_amdgcn_sad_u8(w[q], 0u, ts);                                  // sum of bytes
-            tt = __builtin_amdgcn_udot4(w[q], 0x03020100u + 0x04040404u * q, tt, false);  // sum of j * byte
-        }
+        adler16(w, ts, tt);
         s += ts;
         t += (uint64_t)p * ts + tt;
     };
@@ -2962,7 +3024,7 @@ __device__ __forceinline__ bool dbg_stop(uint32_t mflags, uint32_t phase, dmx_bl
 // and is zeroed again, L.ntok (zero until the walk) the count.  Two barriers.
 __device__ __forceinline__ int32_t block_chain(MatchLDS& L, uint32_t bn, int32_t max_chain, uint32_t mflags,
                                                uint32_t tid) {
-    const int32_t dk = (mflags >> 16) & 0xFFu ? (int32_t)((mflags >> 16) & 0xFFu) : (int32_t)DMX_DEEP_CHAIN;
+    const int32_t dk = deep_chain_of(mflags);
     if (!(mflags & 8u) || max_chain <= 0 || max_chain >= dk) return max_chain;
     const uint32_t nvalid = bn > 2 ? bn - 2 : 0;
     uint32_t* SB = L.hist;
@@ -2981,12 +3043,7 @@ __device__ __forceinline__ int32_t block_chain(MatchLDS& L, uint32_t bn, int32_t
         if ((tid & 63) == 0) atomicAdd(&L.ntok, c);
     }
     __syncthreads();
-    uint32_t ns = 0;
-    for (uint32_t s = 0; s < 16; s++) {
-        const uint32_t lo = s << 11;
-        ns += nvalid > lo ? min(nvalid - lo, 256u) : 0u;
-    }
-    return 4 * L.ntok < ns ? dk : max_chain;
+    return 4 * L.ntok < deep_samples(nvalid) ? dk : max_chain;
 }
 
 // NBX > 3: the exhaustive parse without a dictionary (max_chain = 0) on NBX-byte chains
@@ -3047,12 +3104,24 @@ __device__ __forceinline__ void match_block(const uint32_t b, const uint8_t* __r
     // -- no separate load of byte 0
     bool uni = true;
     uint32_t cb = 0x100u;
+    // Adler-32 partial sums from the staged registers: as = the sum of this thread's bytes,
+    // at = the sum of (offset in block) * byte.  A thread stages two chunks below DMX_BLK (the
+    // slack chunks past it are zero), so at <= 255 * (16 * (16368 + 32752) + 240) < 2^28: 32
+    // bits per thread and per row of 16 lanes, 64 only across the wave (wave_sum_u32_wide).
+    uint32_t as = 0, at = 0;
     for (uint32_t k = tid; k < DATA_WORDS / 4; k += MT) {   // 16-byte chunks
         const uint32_t p = k << 4;
         uint4 v;
         if (early && k < 2 * MT) v = k < MT ? v0 : v1;
         else v = stage16(d, p, bn, aligned16);
         *reinterpret_cast<uint4*>(&L.data[k << 2]) = v;
+        {   // bytes past bn are zero in v
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+            uint32_t ts = 0, tt = 0;
+            adler16(w, ts, tt);
+            as += ts;
+            at += p * ts + tt;
+        }
         // run-dominated blocks take the run_len search (search_positions<.., true>): count the
         // 16-byte chunks that are one repeated byte
         const bool rep = v.x == v.y && v.y == v.z && v.z == v.w && v.x == (v.x & 0xFFu) * 0x01010101u;
@@ -3069,6 +3138,10 @@ __device__ __forceinline__ void match_block(const uint32_t b, const uint8_t* __r
     }
     runny = wave_sum_u32(runny);
     if (lane == 0) L.wexit[wave] = runny;   // free until the walk; published by the barriers below
+    // this wave's Adler sums (uniform), added to the block's after the next barrier: thread 0
+    // zeroed L.adl_s / L.adl_t above
+    const uint32_t adl_ws = wave_sum_u32(as);
+    const uint64_t adl_wt = wave_sum_u32_wide(at);
     // DMX_F_DICT: the chain kernel already sorted this block; the history kernel's
     // results (bucket order) wait in the block's token slots until P3
     const uint32_t* hbk = DICT ? tok_g + (uint64_t)b * DMX_BLK : nullptr;
@@ -3080,6 +3153,7 @@ __device__ __forceinline__ void match_block(const uint32_t b, const uint8_t* __r
             reinterpret_cast<uint4*>(L.sorted)[k] = reinterpret_cast<const uint4*>(Sg)[k];
         for (uint32_t k = tid; k < DMX_BLK / 32; k += MT) L.lit[k] = 0;
         __syncthreads();
+        if (lane == 0) { atomicAdd(&L.adl_s, (unsigned long long)adl_ws); atomicAdd(&L.adl_t, (unsigned long long)adl_wt); }
         kb = block_chain(L, bn, max_chain, mflags, tid);
         if (kb <= 0 || kb > KD) {   // bucket starts, as sort_positions finds them
             for (uint32_t k = tid; k < nv; k += MT) {
@@ -3111,34 +3185,28 @@ __device__ __forceinline__ void match_block(const uint32_t b, const uint8_t* __r
             for (uint32_t k = tid; k < DMX_HIST; k += MT) hist_g[(uint64_t)b * DMX_HIST + k] = L.hist[k];
             return;
         }
+        if (lane == 0) { atomicAdd(&L.adl_s, (unsigned long long)adl_ws); atomicAdd(&L.adl_t, (unsigned long long)adl_wt); }
         uint32_t nrun0 = 0;
 #pragma unroll
         for (int w = 0; w < MW; w++) nrun0 += L.wexit[w];
+        // DMX_F_DEEP: the counting sort hashes the depth statistic's samples itself and takes
+        // the statistic along (sort_dk) when its outcome cannot change what the sort does:
+        // both depths at most KD, so no bucket starts either way.  Every other case (deeper
+        // chains, the exhaustive parse) asks block_chain first.
+        const int32_t dk = deep_chain_of(mflags);
+        const bool insort = NBX == 3 && (mflags & 8u) && max_chain > 0 && max_chain < dk && dk <= KD;
+        const int32_t sort_dk = insort ? dk : 0;
+        if (!insort) kb = block_chain(L, bn, max_chain, mflags, tid);
         // the exhaustive parse's first sort (trigram chains for the gram pass) needs no bucket
         // starts: the 4-byte sort makes the search's (max_chain 1 here only skips them)
-        kb = block_chain(L, bn, max_chain, mflags, tid);
         const int32_t mc0 = (NBX > 3 && !DICT) ? 1 : kb;
-        if (nrun0 * 4 >= ((bn + 15) >> 4)) sort_positions<false, true>(L, bn, mc0, tid, dbg != nullptr, tp0);
-        else sort_positions<false, false>(L, bn, mc0, tid, dbg != nullptr, tp0);
+        const int32_t ks = nrun0 * 4 >= ((bn + 15) >> 4)
+                               ? sort_positions<false, true, 3, NBX == 3>(L, bn, mc0, tid, dbg != nullptr, tp0, sort_dk)
+                               : sort_positions<false, false, 3, NBX == 3>(L, bn, mc0, tid, dbg != nullptr, tp0, sort_dk);
+        if (insort) kb = ks;
     }
 
     if (dbg_stop(mflags, 1, info, hist_g, b, bn, tid)) return;
-    {   // Adler-32 partial sums of this block
-        uint64_t s = 0, t = 0;
-        const uint32_t lo = tid << 5;   // 32 bytes per thread, read as two 16-byte vectors
-        const uint4 v0 = *reinterpret_cast<const uint4*>(&L.data[lo >> 2]);
-        const uint4 v1 = *reinterpret_cast<const uint4*>(&L.data[(lo >> 2) + 4]);
-        const uint32_t w[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-#pragma unroll
-        for (uint32_t j = 0; j < 32; j++) {   // bytes past bn are zero in LDS
-            const uint32_t c = (w[j >> 2] >> (8 * (j & 3))) & 0xFFu;
-            s += c;
-            t += (uint64_t)(lo + j) * c;
-        }
-        s = wave_sum_u64(s);
-        t = wave_sum_u64(t);
-        if (lane == 0) { atomicAdd(&L.adl_s, (unsigned long long)s); atomicAdd(&L.adl_t, (unsigned long long)t); }
-    }
 
     // ---- P0' (the exhaustive parse, no dictionary): 4-byte chains.  Every match of 4 or
     // more bytes is between positions with the same first 4 bytes, so the exhaustive search
@@ -3273,22 +3341,41 @@ __device__ __forceinline__ void match_block(const uint32_t b, const uint8_t* __r
         const uint32_t nvalid = bn > 2 ? bn - 2 : 0;
         uint4 dv[4], pv[4];
         if (kb > 0 && kb <= KE) {
+            // No branches and no tests: a nibble of 0 reads the entry's own slot, so its
+            // distance comes out as 0, and so do the entries past nvalid -- the search zeroed
+            // all 4096 nibble words and writes only those of entries below nvalid (their
+            // position slots hold anything, but S[k] - S[k] is 0 all the same).  The eight
+            // reads of a chunk are issued together; chain entries lie in position order, so
+            // the 16-bit differences never borrow (and the packed subtract keeps them apart).
             const uint32_t* NW = nib_words(L);
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 const uint32_t c = tid + (uint32_t)j * MT;   // 8 entries per 16-byte chunk
-                const bool in = c * 8 < nvalid;
-                pv[j] = in ? reinterpret_cast<const uint4*>(L.sorted)[c] : make_uint4(0, 0, 0, 0);
-                const uint32_t nw = in ? NW[c] : 0u;
+                pv[j] = reinterpret_cast<const uint4*>(L.sorted)[c];
+                const uint32_t nw = NW[c];
                 const uint32_t pw[4] = {pv[j].x, pv[j].y, pv[j].z, pv[j].w};
-                uint32_t dw[4] = {0, 0, 0, 0};
+                // 2 j of the even and of the odd entries, a byte each: the byte offset of
+                // S[k - j] is then one subtract with a byte operand
+                // (through an empty asm: else the compiler undoes this into a shift, a mask
+                // and a subtract per entry)
+                uint32_t j2[2] = {(nw << 1) & 0x1E1E1E1Eu, (nw >> 3) & 0x1E1E1E1Eu};
+                asm("" : "+v"(j2[0]), "+v"(j2[1]));
+                const uint8_t* S8 = reinterpret_cast<const uint8_t*>(L.sorted);
+                uint32_t cs[8];   // S[k - j] of the chunk's entries
 #pragma unroll
                 for (int e = 0; e < 8; e++) {
-                    const uint32_t jj = (nw >> (4 * e)) & 15u, kk = c * 8 + (uint32_t)e;
-                    uint32_t dist = 0;
-                    if (jj == NIB_HIST) dist = DICT ? (hbk[kk] & 0xFFFFu) : 0u;
-                    else if (jj) dist = ((pw[e >> 1] >> (16 * (e & 1))) & 0xFFFFu) - (uint32_t)L.sorted[kk - jj];
-                    dw[e >> 1] |= dist << (16 * (e & 1));
+                    uint32_t jj = (j2[e & 1] >> (8 * (e >> 1))) & 0xFFu;
+                    if (DICT) jj = jj == 2u * NIB_HIST ? 0u : jj;   // (the history's distance: below)
+                    cs[e] = (uint32_t)*reinterpret_cast<const uint16_t*>(S8 + (c * 16 + 2 * (uint32_t)e - jj));
+                }
+                uint32_t dw[4];
+#pragma unroll
+                for (int q = 0; q < 4; q++) dw[q] = pk_sub_u16(pw[q], cs[2 * q] | (cs[2 * q + 1] << 16));
+                if (DICT) {
+#pragma unroll
+                    for (int e = 0; e < 8; e++)
+                        if (((nw >> (4 * e)) & 15u) == NIB_HIST)
+                            dw[e >> 1] |= (hbk[c * 8 + (uint32_t)e] & 0xFFFFu) << (16 * (e & 1));
                 }
                 dv[j] = make_uint4(dw[0], dw[1], dw[2], dw[3]);
             }
@@ -3299,19 +3386,35 @@ __device__ __forceinline__ void match_block(const uint32_t b, const uint8_t* __r
                 const bool in = c * 8 < nvalid;
                 dv[j] = in ? reinterpret_cast<const uint4*>(pg)[c] : make_uint4(0, 0, 0, 0);
                 pv[j] = in ? reinterpret_cast<const uint4*>(L.sorted)[c] : make_uint4(0, 0, 0, 0);
+                // pg's slots past nvalid hold an earlier launch's distances: zero those of the
+                // one chunk that nvalid cuts (masks from uniform values), so that a distance
+                // other than 0 means a valid entry
+                if (c == nvalid >> 3) {
+                    const uint32_t cut = nvalid & 7u;   // its valid entries (0: the chunk is not loaded)
+                    uint32_t dw[4] = {dv[j].x, dv[j].y, dv[j].z, dv[j].w};
+#pragma unroll
+                    for (uint32_t q = 0; q < 4; q++) dw[q] &= cut >= 2 * q + 2 ? ~0u : cut == 2 * q + 1 ? 0xFFFFu : 0u;
+                    dv[j] = make_uint4(dw[0], dw[1], dw[2], dw[3]);
+                }
             }
         }
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-            const uint32_t dw[4] = {dv[j].x, dv[j].y, dv[j].z, dv[j].w}, pw[4] = {pv[j].x, pv[j].y, pv[j].z, pv[j].w};
+            const uint32_t dw[4] = {dv[j].x, dv[j].y, dv[j].z, dv[j].w};
+            // the slots' byte offsets, 2 * position, of two entries at once: a valid position
+            // is below 32768, so the low half does not carry (kept from the compiler, which
+            // splits this into a shift and a mask per entry)
+            uint32_t p2[4] = {pv[j].x << 1, pv[j].y << 1, pv[j].z << 1, pv[j].w << 1};
+            asm("" : "+v"(p2[0]), "+v"(p2[1]), "+v"(p2[2]), "+v"(p2[3]));
 #pragma unroll
             for (int e = 0; e < 8; e++) {
                 // only matches (distance > 0): P3 reads S[p] for match tokens alone, so a
-                // literal position keeps whatever the slot held
-                const uint32_t kk = (tid + (uint32_t)j * MT) * 8 + (uint32_t)e;
+                // literal position keeps whatever the slot held.  One test per store: only
+                // entries below nvalid have a distance other than 0 (both branches above)
                 const uint32_t d16 = (dw[e >> 1] >> (16 * (e & 1))) & 0xFFFFu;
-                if (kk < nvalid && d16 != 0) L.sorted[(pw[e >> 1] >> (16 * (e & 1))) & 0xFFFFu] = (uint16_t)d16;
+                const uint32_t o2 = (e & 1) ? p2[e >> 1] >> 16 : p2[e >> 1] & 0xFFFFu;
+                if (d16 != 0) *reinterpret_cast<uint16_t*>(reinterpret_cast<uint8_t*>(L.sorted) + o2) = (uint16_t)d16;
             }
         }
     }
