@@ -664,20 +664,23 @@ static void orc_plan_split(const uint32_t* tok, int ntok, int bn, orc_split_plan
 /* ---- 7b. incompressible-block check (DMX_F_STORE_CHECK) --------------
  *
  * An encoder policy, not part of the reference (whose parse always runs): a block is
- * emitted stored, without a parse, when its bytes look like noise by three integer
+ * emitted stored, without a parse, when its bytes look like noise by four integer
  * statistics both sides compute exactly:
  *   ones_k = number of bytes among the first 4096 with bit k set, k = 0..7
- *   S2     = sum over byte values c of h[c]^2, h = histogram of the bytes at EVEN positions
- *            (m = (bn + 1) / 2 of them)
+ *   S2     = sum over byte values c of h[c]^2, h = histogram of the bytes at the positions
+ *            p = 0 (mod s), s = 8 / 4 / 2 / 1 for bn >= 32768 / 16384 / 8192 / 4096
+ *            (m = ceil(bn / s) >= 4096 of them)
  *   x(p)   = (d[p] | d[p+1] << 8 | d[p+2] << 16 | d[p+3] << 24) * 0x9E3779B1 (32 bits),
- *            p = 0 .. bn - 4; the 4-gram at p is SAMPLED when bit 13 of x(p) is clear (a
- *            content-defined half: a repeated 4-gram is sampled at both places)
- *   q      = number of sampled positions; coll = q - |{ x(p) >> 14 : p sampled }|
+ *            p = 0 .. bn - 4 (no 4-gram runs past the block's end); the 4-gram at p is
+ *            SAMPLED when bits 11..13 of x(p) are clear (a content-defined eighth: a
+ *            repeated 4-gram is sampled at both places)
+ *   q      = number of sampled positions; coll = q - |{ x(p) >> 15 : p sampled }| (17 bits)
  * stored iff bn >= 4096, 8 * |2 * ones_k - 4096| <= 4096 for every k (a cheap first test on
- * an eighth of a block: text, runs and anything 7-bit fail it), 256 * S2 <= m^2 + m^2 / 16 + 256 * m (noise gives about
- * m^2 + 255 m), 4 * q >= bn, and 64 * coll <= 5 * q (noise: ~512 at bn = 32 768, threshold
- * ~1 280).  A block of repeats with a flat byte histogram (0, 1, ..., 255 cycled) fails the
- * last test.
+ * an eighth of a full block: text, runs and anything 7-bit fail it),
+ * 256 * S2 <= m^2 + (m^2 >> 4) + 256 * m (noise gives about m^2 + 255 m), 16 * q >= bn, and
+ * 64 * coll <= 4 * q (noise: ~64 at bn = 32 768, threshold ~256).  A block of repeats with a
+ * flat byte histogram (0, 1, ..., 255 cycled) fails the last test.  Every comparison holds
+ * with equality; tests/test_store_check_threshold.py has a block on each bound.
  */
 int dmx_oracle_store_check(const uint8_t* d, int bn) {
     if (bn < 4096) return 0;

@@ -144,6 +144,10 @@ def test_gpu_stream_equals_oracle(enc, k, lazy, split, dct):
     z, _ = enc.compress_bytes(data, max_chain=k, flags=fl)
     assert z == O.compress(data, max_chain=k, lazy=lazy, split=split, dict=dct, store_check=True)
     assert zlib.decompress(z) == data
+    # the decision itself, per block (the stream cannot show it: K2 stores parsed noise too)
+    checked = [O.store_check(data[o:o + 32768]) for o in range(0, len(data), 32768)]
+    nt, _, _ = enc.blocks(len(checked))
+    assert [int(x) == 0 for x in nt] == checked
     assert D.compress(data, max_chain=k, lazy=lazy, split=split, dict=dct, store_check=True) == z
 
 
