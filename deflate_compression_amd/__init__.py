@@ -11,6 +11,7 @@ include/dmx.h).  This module is a thin ctypes layer:
     compress(data, sw=32768, max_chain=0) -> bytes        host buffer convenience (gzip=True: a .gz member,
                                                           bgzf=True: BGZF, a gzip member per block)
     bgzf_index(z) / inflate_bgzf_gpu(z)                   a BGZF file's members, decoded in parallel on the GPU
+    decompress_bgzf(z) -> bytes                           the same from and to host buffers (any BGZF file)
     Encoder                                               device-resident encodes
 
 There is no CPU fallback: if libdmx.so is missing the import of this module fails,
@@ -25,7 +26,7 @@ import struct
 __all__ = [
     "DeflateError", "Opts", "Result", "Encoder", "lib", "compress", "deflate_compress",
     "deflate_decompress", "max_compressed", "adler32_combine", "gen_text", "gen_random",
-    "COMPRESS_STATS", "E", "DMX_F_HEADER", "DMX_F_TRAILER", "DMX_F_FINAL", "DMX_ZLIB", "DMX_F_LAZY", "DMX_F_EXACT_SORT", "DMX_F_SPLIT", "DMX_F_DICT", "DMX_F_STORE_CHECK", "DMX_F_DEEP", "DMX_F_GZIP", "DMX_GZIP", "DMX_F_BGZF", "DMX_BGZF", "crc32_combine", "crc32_geometry", "bgzf_index", "inflate_bgzf_gpu", "inflate_gpu", "inflate_gpu_chained", "ref_estimates",
+    "COMPRESS_STATS", "E", "DMX_F_HEADER", "DMX_F_TRAILER", "DMX_F_FINAL", "DMX_ZLIB", "DMX_F_LAZY", "DMX_F_EXACT_SORT", "DMX_F_SPLIT", "DMX_F_DICT", "DMX_F_STORE_CHECK", "DMX_F_DEEP", "DMX_F_GZIP", "DMX_GZIP", "DMX_F_BGZF", "DMX_BGZF", "crc32_combine", "crc32_geometry", "bgzf_index", "inflate_bgzf_gpu", "decompress_bgzf", "crc32_ranges", "DMX_BGZF_MAX_ISIZE", "inflate_gpu", "inflate_gpu_chained", "ref_estimates",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -45,6 +46,7 @@ DMX_F_GZIP = 512
 DMX_GZIP = DMX_ZLIB | DMX_F_GZIP
 DMX_F_BGZF = 1024
 DMX_BGZF = DMX_F_BGZF | DMX_F_FINAL
+DMX_BGZF_MAX_ISIZE = 65536
 _M = 1 << 24
 # src/include/global_errors.h:24-35 and src/include/deflate_errors.h:9-22
 E = {
@@ -126,6 +128,10 @@ def lib() -> ctypes.CDLL:
         "dmx_crc32_async": ([vp, vp, u64, vp, vp], ctypes.c_int),
         "dmx_crc32_blocks_async": ([vp, vp, u64, i32, vp, vp], ctypes.c_int),
         "dmx_bgzf_index": ([vp, u64, vp, vp, u32, u32p, ctypes.POINTER(u64)], ctypes.c_int),
+        "dmx_bgzf_index_max": ([vp, u64, u32, vp, vp, u32, u32p, ctypes.POINTER(u64)], ctypes.c_int),
+        "dmx_bgzf_decode_host": ([vp, u64, vp, u64, ctypes.POINTER(u64), ctypes.c_int], ctypes.c_int),
+        "dmx_crc32_ranges_async": ([vp, u64, vp, u32, vp, vp, vp], ctypes.c_int),
+        "dmx_inflate_members_async": ([vp, u64, vp, u32, vp, u64, vp, vp, vp], ctypes.c_int),
         "dmx_crc32_combine": ([u32, u32, u64], u32),
         "dmx_crc32_geometry": ([u32p, u32p], None),
         "dmx_fd_last_stats": ([ctypes.POINTER(FdStats)], ctypes.c_int),
@@ -269,64 +275,109 @@ def inflate_gpu(z, out_cap: int, index=None, nblk: int = 0, stream=None):
     return out[:olen], status
 
 
-def bgzf_index(z):
-    """The members of a BGZF file in host memory (dmx_bgzf_index): (index, crcs, total) -- index
+def bgzf_index(z, max_member: int = 32768):
+    """The members of a BGZF file in host memory (dmx_bgzf_index_max): (index, crcs, total) -- index
     a uint8 numpy array of nblk x 24 B dmx_iblock records (one per member with data: the first
     bit of its DEFLATE data, output offset and length), crcs the members' stored CRC-32s
-    (uint32[nblk]), total the decoded length.  Members of more than 32768 input bytes (htslib's
-    default blocks) raise DeflateError(-E_RANGE).  Pure host code: no GPU needed."""
+    (uint32[nblk]), total the decoded length.  A member of more than max_member input bytes raises
+    DeflateError(-E_RANGE): the default 32768 is what inflate_gpu's indexed mode takes, 65536
+    (DMX_BGZF_MAX_ISIZE) is every member the format allows, htslib's 65280-byte blocks included
+    (inflate_bgzf_gpu, dmx_inflate_members_async).  Pure host code: no GPU needed."""
     import numpy as np
     L = lib()
     p, n, keep = _buf(z)
     nb, tot = ctypes.c_uint32(0), ctypes.c_uint64(0)
-    r = L.dmx_bgzf_index(p, n, None, None, 0, ctypes.byref(nb), ctypes.byref(tot))
+    r = L.dmx_bgzf_index_max(p, n, max_member, None, None, 0, ctypes.byref(nb), ctypes.byref(tot))
     if r != 0 and r != -E["E_SZ"]:
         raise DeflateError(r, "dmx_bgzf_index")
     idx = np.zeros(max(nb.value, 1) * 24, np.uint8)
     crc = np.zeros(max(nb.value, 1), np.uint32)
-    _check(L.dmx_bgzf_index(p, n, ctypes.c_void_p(idx.ctypes.data), ctypes.c_void_p(crc.ctypes.data), nb.value,
-                            ctypes.byref(nb), ctypes.byref(tot)), "dmx_bgzf_index")
+    _check(L.dmx_bgzf_index_max(p, n, max_member, ctypes.c_void_p(idx.ctypes.data), ctypes.c_void_p(crc.ctypes.data),
+                                nb.value, ctypes.byref(nb), ctypes.byref(tot)), "dmx_bgzf_index")
     del keep
     return idx[:nb.value * 24], crc[:nb.value], int(tot.value)
 
 
+def _inflate_status(st):
+    """(status, out_len) of a 16-byte dmx_inflate_status CUDA tensor"""
+    import numpy as np
+    h = st.cpu().numpy()
+    return int(np.frombuffer(h[:4].tobytes(), np.int32)[0]), int(np.frombuffer(h[8:16].tobytes(), np.uint64)[0])
+
+
+def crc32_ranges(t, index, nblk: int, stream=None):
+    """CRC-32 of the nblk ranges [out_off, out_off + out_len) of a uint8 CUDA tensor that a
+    device index lists (a uint8 CUDA tensor of nblk x 24 B dmx_iblock records; out_len 0..65536,
+    any order, any offset), computed on the device in one launch (dmx_crc32_ranges_async): an
+    int32 CUDA tensor of nblk words (view as uint32 on the host).  An entry outside the tensor or
+    longer than 65536 raises DeflateError(-E_RANGE)."""
+    import torch
+    w = torch.zeros(max(nblk, 1), dtype=torch.int32, device=t.device)
+    st = torch.zeros(16, dtype=torch.uint8, device=t.device)
+    s = stream if stream is not None else torch.cuda.current_stream(t.device).cuda_stream
+    n = t.numel()
+    with torch.cuda.device(t.device):
+        _check(lib().dmx_crc32_ranges_async(ctypes.c_void_p(t.data_ptr() if n else 0), n, ctypes.c_void_p(index.data_ptr()),
+                                            nblk, ctypes.c_void_p(w.data_ptr()), ctypes.c_void_p(st.data_ptr()),
+                                            ctypes.c_void_p(s)), "dmx_crc32_ranges_async")
+        torch.cuda.synchronize(t.device)
+    status, _ = _inflate_status(st)
+    if status:
+        raise DeflateError(status, "dmx_crc32_ranges_async")
+    return w[:nblk]
+
+
 def inflate_bgzf_gpu(z, verify: bool = True, encoder=None):
-    """Inflate a BGZF file (host bytes) on the GPU, every member in parallel: the host index
-    (bgzf_index), inflate_gpu with it, and with `verify` the CRC-32 of every decoded member
-    (Encoder.crc32_blocks) compared on the device against the members' stored values --
-    DeflateError(-E_CRC) on a mismatch.  The per-block CRC needs equal-sized members (all but
-    the last with the same ISIZE): a file that is not raises ValueError unless verify=False.
-    encoder: an Encoder to run the CRC on (one is made otherwise).  Returns a uint8 CUDA tensor."""
+    """Inflate a BGZF file (host bytes) on the GPU, every member in parallel: the host index with
+    the format's own bound on a member (bgzf_index(z, 65536): htslib's 65280-byte blocks, short
+    and empty members in any mix), then dmx_inflate_members_async -- the indexed decode and, with
+    `verify`, the CRC-32 of every decoded member compared on the device against its stored value:
+    DeflateError(-E_CRC) on a mismatch, the decode's status where the decode failed.
+    encoder: an Encoder whose device to use (cuda:0 otherwise).  Returns a uint8 CUDA tensor."""
     import numpy as np
     import torch
-    idx, crcs, total = bgzf_index(z)
+    idx, crcs, total = bgzf_index(z, DMX_BGZF_MAX_ISIZE)
     nblk = crcs.size
-    dev = f"cuda:{encoder.device if encoder is not None else 0}"
+    dev = torch.device(f"cuda:{encoder.device if encoder is not None else 0}")
     if nblk == 0:
         return torch.empty(0, dtype=torch.uint8, device=dev)
-    lens = idx.view(np.uint32).reshape(nblk, 6)[:, 4]
-    sw = int(lens[0])
-    uniform = bool((lens[:-1] == sw).all()) and int(lens[-1]) <= sw
-    if verify and not uniform:
-        raise ValueError("inflate_bgzf_gpu: members of different sizes cannot be verified (verify=False)")
     b = bytes(z) if not isinstance(z, np.ndarray) else z
     zt = torch.from_numpy(np.frombuffer(b, dtype=np.uint8).copy()).to(dev)
-    out, st = inflate_gpu(zt, total, torch.from_numpy(idx.copy()).to(dev), nblk)
-    if st:
-        raise DeflateError(st, "inflate_gpu")
-    if out.numel() != total:
-        raise DeflateError(-E["E_LEN"], "inflate_gpu")
-    if verify:
-        enc = encoder if encoder is not None else Encoder(0, max_input=1)
-        try:
-            got = enc.crc32_blocks(out, sw)
-        finally:
-            if encoder is None:
-                enc.close()
-        want = torch.from_numpy(crcs.view(np.int32).copy()).to(dev)
-        if not torch.equal(got, want):
-            raise DeflateError(-E["E_CRC"], "inflate_bgzf_gpu")
+    ix = torch.from_numpy(idx.copy()).to(dev)
+    want = torch.from_numpy(crcs.view(np.int32).copy()).to(dev)
+    out = torch.empty(total, dtype=torch.uint8, device=dev)
+    st = torch.zeros(16, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        s = torch.cuda.current_stream(dev).cuda_stream
+        _check(lib().dmx_inflate_members_async(ctypes.c_void_p(zt.data_ptr()), zt.numel(), ctypes.c_void_p(ix.data_ptr()),
+                                               nblk, ctypes.c_void_p(out.data_ptr()), total,
+                                               ctypes.c_void_p(want.data_ptr() if verify else 0),
+                                               ctypes.c_void_p(st.data_ptr()), ctypes.c_void_p(s)),
+               "dmx_inflate_members_async")
+        torch.cuda.synchronize(dev)
+    status, olen = _inflate_status(st)
+    if status:
+        raise DeflateError(status, "inflate_bgzf_gpu")
+    if olen != total:
+        raise DeflateError(-E["E_LEN"], "inflate_bgzf_gpu")
     return out
+
+
+def decompress_bgzf(z, verify: bool = True) -> bytes:
+    """Decompress a BGZF file (host bytes) on the GPU into host bytes (dmx_bgzf_decode_host): any
+    member the format allows, with `verify` every member's CRC-32 checked on the device
+    (DeflateError(-E_CRC)).  An empty file, or one of empty members only, gives b""."""
+    L = lib()
+    p, n, keep = _buf(z)
+    olen = ctypes.c_uint64(0)
+    r = L.dmx_bgzf_decode_host(p, n, None, 0, ctypes.byref(olen), 1 if verify else 0)   # the decoded length
+    if r != -E["E_SZ"]:
+        _check(r, "dmx_bgzf_decode_host")
+        return b""
+    out = ctypes.create_string_buffer(olen.value)
+    _check(L.dmx_bgzf_decode_host(p, n, out, olen.value, ctypes.byref(olen), 1 if verify else 0), "dmx_bgzf_decode_host")
+    del keep
+    return out.raw[:olen.value]
 
 
 def inflate_gpu_chained(z, out_cap: int, index, nblk: int, stream=None, work=None):

@@ -369,6 +369,182 @@ extern "C" int dmx_crc32_blocks_async(dmx_ctx* c, const void* d_in, uint64_t n, 
     return 0;
 }
 
+// ---- CRC-32 over index ranges (the members of a BGZF file: any offset, 0..65536 bytes each) ----
+//
+//   dmx_crc_ranges_kernel  the blocks kernel with the block's geometry read from an index entry
+//                          {out_off, out_len} instead of computed from b and sw.  A workgroup takes
+//                          an entry and stages it in pieces of at most CRC_S bytes, from the 16-byte
+//                          group that holds its first byte: a range of 65 536 bytes at an odd address
+//                          is two whole pieces and one of 1..15 bytes.  Every piece is staged, looked
+//                          up and lane-folded as a block is (in piece-local 32-bit offsets, through
+//                          crc_load16_blk), and thread 0 folds piece by piece, R = R x^(8 CRC_S) xor
+//                          R(piece).  Only the last piece has zeros behind its data, Z < CRC_S of
+//                          them, divided out with the g_crc_unshift tables as in the blocks kernel.
+//                          The affine term depends on the entry's length, so the host cannot pass
+//                          it: 0xFFFFFFFF x^(8 len) is the product of two more table entries
+//                          (g_crc_shift: len <= 65 536 = 256 x 256), computed with x^-(8 Z) by wave 0
+//                          while the piece's loads fly.  (dmx_crc32_affine itself is host and device
+//                          code, but its square-and-multiply is about 37 dependent multiplications,
+//                          more than the lookups of a whole piece: the tables make it one.)
+//                          The flat sequence of pieces of a workgroup's entries is pipelined as the
+//                          blocks are: the next piece's loads fly during this one's lookups.
+//                          An empty entry is one piece without data (no load, no lookup, value 0); an
+//                          entry out of range is the same and writes nothing.
+//                          want == NULL: crc[k] receives entry k's value.  want != NULL (the check of
+//                          dmx_inflate_members_async): the value is compared with want[k], a
+//                          difference sets -E_CRC unless a status is there -- and a status that is
+//                          there at the start ends the kernel at once: the decode before it failed,
+//                          and its index may be unsound.
+struct CrcShift {
+    uint32_t lo[256];   // 0xFFFFFFFF x^(8 v)
+    uint32_t hi[257];   // x^(8 256 v)
+};
+static constexpr CrcShift crc_make_shift() {
+    CrcShift U = {};
+    uint32_t x8 = DMX_CRC_ONE >> 1;
+    for (int k = 0; k < 3; k++) x8 = crc_cmul(x8, x8);   // x^8
+    uint32_t p = 0xFFFFFFFFu, q = DMX_CRC_ONE;
+    for (int v = 0; v < 256; v++) { U.lo[v] = p; p = crc_cmul(p, x8); q = crc_cmul(q, x8); }
+    const uint32_t x2048 = q;    // x^(8 256)
+    p = DMX_CRC_ONE;
+    for (int v = 0; v < 257; v++) { U.hi[v] = p; p = crc_cmul(p, x2048); }
+    return U;
+}
+static_assert(DMX_BGZF_MAX_ISIZE == 256 * 256, "a length is lo + 256 hi with hi <= 256");
+static_assert(2 * CRC_S == DMX_BGZF_MAX_ISIZE, "a range is at most two spans and one 16-byte group");
+__device__ const CrcShift g_crc_shift = crc_make_shift();
+
+__global__ __launch_bounds__(CRC_T) void dmx_crc_ranges_kernel(const uint8_t* __restrict__ in, uint64_t n,
+                                                               const dmx_iblock* __restrict__ index, uint32_t nblk,
+                                                               uint32_t* __restrict__ crc, const uint32_t* __restrict__ want,
+                                                               dmx_inflate_status* st) {
+    __shared__ __attribute__((aligned(16))) uint32_t tab[CRC_NS * 256];
+    __shared__ __attribute__((aligned(16))) uint32_t stage[CRC_T * CRC_ROW];
+    __shared__ uint32_t wred[CRC_T / 64];
+    __shared__ int32_t st0;
+    const uint32_t tid = threadIdx.x;
+    if (tid == 0) st0 = want ? st->status : 0;   // one read: the whole workgroup stays or leaves
+    __syncthreads();
+    if (st0 != 0) return;
+    for (uint32_t i = tid; i < CRC_NS * 256; i += CRC_T) tab[i] = (&g_crc.t[0][0])[i];
+    const uint32_t klane = g_crc.lane[tid];
+    constexpr uint32_t XS = crc_xspan();
+    // piece j of entry k: its aligned base, the data's bytes [lo, hi) from there (hi <= CRC_S),
+    // the entry's pieces and length; false: the entry is out of range (then one piece, no data)
+    auto geom = [&](uint32_t k, uint32_t j, const uint8_t*& base, uint32_t& lo, uint32_t& hi, uint32_t& np, uint32_t& len) {
+        const uint64_t off = index[k].out_off;
+        len = index[k].out_len;
+        const bool ok = len <= DMX_BGZF_MAX_ISIZE && off <= n && len <= n - off;
+        uint32_t elo = 0, ehi = 0;   // the whole entry from its aligned base: ehi <= 15 + 65 536
+        base = in;
+        if (ok && len) {
+            const uint8_t* p = in + off;
+            elo = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 15);
+            base = p - elo;
+            ehi = elo + len;
+        }
+        np = ehi > CRC_S ? (ehi + CRC_S - 1) / CRC_S : 1u;
+        base += (size_t)j * CRC_S;
+        lo = j ? 0u : elo;
+        hi = ehi - j * CRC_S < CRC_S ? ehi - j * CRC_S : (uint32_t)CRC_S;   // (j < np: ehi > j CRC_S, or both are 0)
+        return ok;
+    };
+    uint4 v[CRC_Q];
+    auto load = [&](uint32_t k, uint32_t j) {
+        const uint8_t* base;
+        uint32_t lo, hi, np, len;
+        geom(k, j, base, lo, hi, np, len);
+#pragma unroll
+        for (uint32_t i = 0; i < CRC_Q; i++) v[i] = crc_load16_blk(base, 16u * (tid + CRC_T * i), lo, hi);
+    };
+    uint32_t k = blockIdx.x, j = 0, acc = 0;   // acc (thread 0): the raw remainder of the entry's pieces so far
+    if (k < nblk) load(k, 0);
+    while (k < nblk) {
+        const uint8_t* base;
+        uint32_t lo, hi, np, len;
+        const bool ok = geom(k, j, base, lo, hi, np, len);
+        const bool last = j + 1 == np;
+        // x^-(8 Z) and the affine term, by wave 0 while the loads fly (thread 0 uses them)
+        uint32_t unshift = 0, affine = 0;
+        if (last && tid < 64) {
+            const uint32_t Z = (CRC_S - hi) & (CRC_S - 1u), l = ok ? len : 0u;   // (no data: R = 0, any factor)
+            unshift = dmx_gf2_mulmod(g_crc_unshift.lo[Z & 255u], g_crc_unshift.hi[Z >> 8]);
+            affine = dmx_gf2_mulmod(g_crc_shift.lo[l & 255u], g_crc_shift.hi[l >> 8]) ^ 0xFFFFFFFFu;
+        }
+#pragma unroll
+        for (uint32_t i = 0; i < CRC_Q; i++) {
+            const uint32_t q = tid + CRC_T * i, sl = q / (CRC_L / 16);
+            if (sl * CRC_L < hi)   // (a slice behind the data is never read)
+                *reinterpret_cast<uint4*>(&stage[sl * CRC_ROW + 4 * (q % (CRC_L / 16))]) = v[i];
+        }
+        __syncthreads();   // (and the tables, the first time)
+        const uint32_t kn = last ? k + gridDim.x : k, jn = last ? 0u : j + 1;
+        if (kn < nblk) load(kn, jn);   // the next piece's loads fly during this one's lookups
+        uint32_t c = 0;
+        if (tid * CRC_L < hi) {
+            const uint4* p = reinterpret_cast<const uint4*>(&stage[tid * CRC_ROW]);
+#pragma unroll
+            for (uint32_t s = 0; s < CRC_L / 16; s++) {
+                const uint4 d = p[s];
+                CRC_STEP16(c, d, tab);
+            }
+        }
+        uint32_t r = dmx_gf2_mulmod(c, klane);
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) r ^= __shfl_xor(r, o);
+        if ((tid & 63) == 0) wred[tid >> 6] = r;
+        __syncthreads();   // (also: every lane has read its slice before the next staging)
+        if (tid == 0) {
+            uint32_t t = 0;
+#pragma unroll
+            for (uint32_t w = 0; w < CRC_T / 64; w++) t ^= wred[w];
+            acc = j ? dmx_gf2_mulmod(acc, XS) ^ t : t;
+            if (last) {
+                const uint32_t val = dmx_gf2_mulmod(acc, unshift) ^ affine;
+                if (!ok) {
+                    if (st) atomicCAS(&st->status, 0, -(int32_t)E_RANGE);
+                } else if (!want) {
+                    crc[k] = val;
+                } else if (val != want[k]) {
+                    atomicCAS(&st->status, 0, -(int32_t)E_CRC);
+                }
+            }
+        }
+        k = kn;
+        j = jn;
+    }
+}
+
+// compute units of the current device (the grid of the ranges kernel, which has no context)
+static uint32_t crc_device_ncu(void) {
+    static uint32_t ncu[64];
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256u;
+    if (!ncu[dev])
+        ncu[dev] = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0
+                       ? (uint32_t)v : 256u;
+    return ncu[dev];
+}
+
+// the launch of dmx_crc32_ranges_async on stream s, and with d_want the check of
+// dmx_inflate_members_async (dmx_inflate_dev.hip).  No scratch: every workgroup writes (or
+// compares) finished values.
+int dmx_crc32_ranges_launch(const void* d_in, uint64_t n, const dmx_iblock* d_index, uint32_t nblk, uint32_t* d_crc,
+                            const uint32_t* d_want, dmx_inflate_status* d_status, hipStream_t s) {
+    if (!nblk) return 0;
+    const uint32_t gmax = 3 * crc_device_ncu();   // 3 workgroups of 52 KiB LDS per CU
+    hipLaunchKernelGGL(dmx_crc_ranges_kernel, dim3(nblk < gmax ? nblk : gmax), dim3(CRC_T), 0, s, (const uint8_t*)d_in,
+                       n, d_index, nblk, d_crc, d_want, d_status);
+    return hipGetLastError() == hipSuccess ? 0 : -(int)E_DEVICE;
+}
+
+extern "C" int dmx_crc32_ranges_async(const void* d_in, uint64_t n, const dmx_iblock* d_index, uint32_t nblk,
+                                      uint32_t* d_crc, dmx_inflate_status* d_status, void* stream) {
+    if ((!d_in && n) || (nblk && (!d_index || !d_crc))) return -(int)E_INVAL;
+    if ((reinterpret_cast<uintptr_t>(d_crc) & 3) != 0) return -(int)E_INVAL;
+    return dmx_crc32_ranges_launch(d_in, n, d_index, nblk, d_crc, NULL, d_status, (hipStream_t)stream);
+}
+
 extern "C" void dmx_crc32_geometry(uint32_t* span, uint32_t* lane_slice) {
     if (span) *span = CRC_S;
     if (lane_slice) *lane_slice = CRC_L;

@@ -95,6 +95,11 @@ static inline hipError_t dmx_malloc(T** p, size_t n) { return dmx_malloc(reinter
 // prints the failing call and returns 1 on an error
 DMX_HIDDEN int hip_fail(hipError_t e, const char* what);
 #define HIPCHK(x) do { if (hip_fail((x), #x)) return -(int)E_DEVICE; } while (0)
+// the launch of the CRC-32 over index ranges (dmx_crc.hip): into d_crc, or with d_want compared
+// on the device (-E_CRC into d_status: dmx_inflate_members_async, dmx_inflate_dev.hip)
+DMX_HIDDEN int dmx_crc32_ranges_launch(const void* d_in, uint64_t n, const dmx_iblock* d_index, uint32_t nblk,
+                                       uint32_t* d_crc, const uint32_t* d_want, dmx_inflate_status* d_status,
+                                       hipStream_t s);
 // the fd pipeline's buffers of a context (dmx_fd.cpp), freed with the context
 DMX_HIDDEN void fdp_free(FdPipe* P);
 

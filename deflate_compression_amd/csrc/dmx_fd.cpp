@@ -81,6 +81,64 @@ extern "C" int dmx_encode_host(const uint8_t* in, uint64_t n, uint8_t* out, uint
     return r;
 }
 
+// Any BGZF file in host memory through HBM (include/dmx.h): the host index with the format's
+// bound on a member, then on the cached context's stream the copies of the file, the index and
+// the members' CRC-32s (one staging buffer: [file | index | CRCs | status], each 16-byte
+// aligned), dmx_inflate_members_async, and the decoded bytes back.
+extern "C" int dmx_bgzf_decode_host(const uint8_t* z, uint64_t zlen, uint8_t* out, uint64_t out_cap, uint64_t* out_len,
+                                    int verify) {
+    if ((!z && zlen) || !out_len || (!out && out_cap)) return -(int)E_INVAL;
+    *out_len = 0;
+    uint32_t nb = 0;
+    uint64_t total = 0;
+    int r = dmx_bgzf_index_max(z, zlen, DMX_BGZF_MAX_ISIZE, NULL, NULL, 0, &nb, &total);
+    if (r && r != -(int)E_SZ) return r;
+    *out_len = total;
+    if (total > out_cap) return -(int)E_SZ;
+    if (!nb) return 0;
+    dmx_iblock* idx = (dmx_iblock*)malloc((size_t)nb * sizeof(dmx_iblock));
+    uint32_t* crc = (uint32_t*)malloc((size_t)nb * sizeof(uint32_t));
+    if (!idx || !crc) {
+        free(idx);
+        free(crc);
+        return -(int)E_MALLOC;
+    }
+    r = dmx_bgzf_index_max(z, zlen, DMX_BGZF_MAX_ISIZE, idx, crc, nb, &nb, &total);
+    const uint64_t o_idx = (zlen + 15) & ~15ull, o_crc = o_idx + (((uint64_t)nb * sizeof(dmx_iblock) + 15) & ~15ull);
+    const uint64_t o_st = o_crc + (((uint64_t)nb * 4 + 15) & ~15ull);
+    const char* dev_s = getenv("DMX_DEVICE");
+    const int dev = dev_s ? atoi(dev_s) : 0;
+    pthread_mutex_lock(&g_mu);
+    int err = 0;
+    dmx_ctx* c = r ? NULL : dmx_cached_ctx(dev, 0, &err);
+    if (!r) r = err;
+    if (!r) r = ensure_buf(&c->d_in, &c->d_in_cap, o_st + sizeof(dmx_inflate_status));
+    if (!r) r = ensure_buf(&c->d_out, &c->d_out_cap, total + 16);
+    if (!r && hip_fail(hipSetDevice(c->device), "hipSetDevice")) r = -(int)E_DEVICE;
+    dmx_inflate_status st = {0, 0, 0};
+    if (!r) {
+        uint8_t* d = (uint8_t*)c->d_in;
+        dmx_inflate_status* d_st = (dmx_inflate_status*)(d + o_st);
+        if (hip_fail(hipMemcpyAsync(d, z, zlen, hipMemcpyHostToDevice, c->stream), "H2D(file)") ||
+            hip_fail(hipMemcpyAsync(d + o_idx, idx, (size_t)nb * sizeof(dmx_iblock), hipMemcpyHostToDevice, c->stream), "H2D(index)") ||
+            hip_fail(hipMemcpyAsync(d + o_crc, crc, (size_t)nb * 4, hipMemcpyHostToDevice, c->stream), "H2D(crc)"))
+            r = -(int)E_DEVICE;
+        if (!r)
+            r = dmx_inflate_members_async(d, zlen, (const dmx_iblock*)(d + o_idx), nb, c->d_out, total,
+                                          verify ? (const uint32_t*)(d + o_crc) : NULL, d_st, c->stream);
+        if (!r && (hip_fail(hipMemcpyAsync(&st, d_st, sizeof(st), hipMemcpyDeviceToHost, c->stream), "D2H(status)") ||
+                   hip_fail(hipStreamSynchronize(c->stream), "hipStreamSynchronize")))
+            r = -(int)E_DEVICE;
+        if (!r && st.status) r = st.status;
+        if (!r && st.out_len != total) r = -(int)E_LEN;
+        if (!r && hip_fail(hipMemcpy(out, c->d_out, total, hipMemcpyDeviceToHost), "D2H")) r = -(int)E_DEVICE;
+    }
+    pthread_mutex_unlock(&g_mu);
+    free(idx);
+    free(crc);
+    return r;
+}
+
 // --- streaming file-in/file-out (the fd API without per-token stats) ---
 // The input is read in chunks of `chunk` bytes (a multiple of sw) straight into pinned
 // buffers; chunk i is copied to the device and encoded while the host reads chunk i+1

@@ -389,12 +389,13 @@ int deflate_decompress(struct string_len* decompr_dat, struct string_len* compr_
  * (SI1 'B', SI2 'C', SLEN 2), so the walk reads headers and trailers only.  The DEFLATE data
  * of a member starts behind its header (gzip_header: FNAME / FCOMMENT / FHCRC are skipped if a
  * writer set them) and its trailer is the member's last 8 bytes. */
-int dmx_bgzf_index(const uint8_t* z, uint64_t zlen, dmx_iblock* idx, uint32_t* crc, uint32_t cap, uint32_t* nblk,
-                   uint64_t* out_len) {
+int dmx_bgzf_index_max(const uint8_t* z, uint64_t zlen, uint32_t max_isize, dmx_iblock* idx, uint32_t* crc,
+                       uint32_t cap, uint32_t* nblk, uint64_t* out_len) {
     if ((!z && zlen) || !nblk || (!idx && cap)) return -(int)E_INVAL;
     uint64_t p = 0, total = 0, cnt = 0;
     *nblk = 0;
     if (out_len) *out_len = 0;
+    if (max_isize < 1 || max_isize > DMX_BGZF_MAX_ISIZE) return -(int)E_RANGE;
     while (p < zlen) {
         const uint8_t* m = z + p;
         const uint64_t left = zlen - p;
@@ -427,7 +428,7 @@ int dmx_bgzf_index(const uint8_t* z, uint64_t zlen, dmx_iblock* idx, uint32_t* c
         const uint8_t* t = m + bsize - 8;
         const uint32_t mcrc = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
         const uint32_t isize = (uint32_t)t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
-        if (isize > DMX_BLK) return -(int)E_RANGE;
+        if (isize > max_isize) return -(int)E_RANGE;
         if (isize) {
             if (cnt < cap) {
                 idx[cnt].bit = 8 * (p + (uint64_t)body);
@@ -445,4 +446,10 @@ int dmx_bgzf_index(const uint8_t* z, uint64_t zlen, dmx_iblock* idx, uint32_t* c
     *nblk = (uint32_t)cnt;
     if (out_len) *out_len = total;
     return cnt > cap ? -(int)E_SZ : 0;
+}
+
+/* the members the one-wave-per-block decoder of dmx_inflate_async takes: ISIZE <= 32768 */
+int dmx_bgzf_index(const uint8_t* z, uint64_t zlen, dmx_iblock* idx, uint32_t* crc, uint32_t cap, uint32_t* nblk,
+                   uint64_t* out_len) {
+    return dmx_bgzf_index_max(z, zlen, DMX_BLK, idx, crc, cap, nblk, out_len);
 }

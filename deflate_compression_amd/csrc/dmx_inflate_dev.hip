@@ -31,6 +31,7 @@
 #include <string.h>
 
 #include "../../include/dmx.h"
+#include "dmx_ctx.h"   // dmx_crc32_ranges_launch
 
 #define IW 32768          // window = LDS ring (stream mode; the indexed mode's ring is IWX)
 #ifndef DMX_IWX
@@ -820,12 +821,16 @@ __device__ __forceinline__ int iblock(InfLDS<W, typename std::conditional<CELL, 
     return err;   // (the caller folds the end of the input in: ib_status)
 }
 
-// CELL: out is the cell buffer (2 bytes a position), out_cap in positions
+// CELL: out is the cell buffer (2 bytes a position), out_cap in positions.  max_len: the largest
+// out_len of an entry -- IW for dmx_inflate_async and for the cells (a reference cell holds a
+// distance below IW, and the chained lists 16-bit offsets), DMX_BGZF_MAX_ISIZE for the members of
+// dmx_inflate_members_async.  Nothing below depends on it (the audit): positions
+// are 32-bit, the ring index is a mask, and sources older than the ring come from d_out.
 template <bool CELL>
 __global__ __launch_bounds__(64) void dmx_inflate_index_kernel(const uint8_t* __restrict__ z, uint64_t zbytes,
                                                                const dmx_iblock* __restrict__ index,
                                                                uint8_t* __restrict__ out, uint64_t out_cap,
-                                                               uint32_t* __restrict__ gtab,
+                                                               uint32_t* __restrict__ gtab, uint32_t max_len,
                                                                dmx_inflate_status* __restrict__ st) {
     // bytes: an 8 KiB ring, 10 KiB of LDS; cells: 4 096 cells, the same 10 KiB.  12 workgroups
     // per CU (151 VGPRs: 3 waves per SIMD), so 3 072 blocks decode at once
@@ -851,7 +856,7 @@ __global__ __launch_bounds__(64) void dmx_inflate_index_kernel(const uint8_t* __
     o.a = 1;
     o.b = 0;
     int err = 0;
-    if (olen > IW || off + olen > out_cap || (bit >> 3) >= zbytes) err = -(int)E_RANGE;
+    if (olen > max_len || off > out_cap || olen > out_cap - off || (bit >> 3) >= zbytes) err = -(int)E_RANGE;
     if (!err) {
         ib_seek(r, bit);
         bool last = false;
@@ -961,12 +966,21 @@ static uint32_t* itab_scratch(hipStream_t s, uint64_t bytes) {
     return (uint32_t*)p;
 }
 
-extern "C" int dmx_inflate_async(const void* d_z, uint64_t zbytes, const dmx_iblock* d_index, uint32_t nblk,
-                                 void* d_out, uint64_t out_cap, dmx_inflate_status* d_status, void* stream) {
-    if (!d_z || !d_out || !d_status || (d_index && !nblk)) return -(int)E_INVAL;
+// The status record's reset.  A kernel, not hipMemsetAsync: captured into a graph (ROCm 7.2), the
+// 16-byte memset node wrote zeros on the first replay only and other bytes on every later one.
+__global__ void dmx_inflate_status_clear_kernel(dmx_inflate_status* __restrict__ st) {
+    st->status = 0;
+    st->reserved = 0;
+    st->out_len = 0;
+}
+
+// the decode of dmx_inflate_async (d_index == NULL: the stream mode) and of
+// dmx_inflate_members_async; max_len: the indexed kernel's bound on an entry's out_len
+static int inflate_launch(const void* d_z, uint64_t zbytes, const dmx_iblock* d_index, uint32_t nblk, void* d_out,
+                          uint64_t out_cap, uint32_t max_len, dmx_inflate_status* d_status, hipStream_t s) {
     if (zbytes > 0xFFFFFFF0ull) return -(int)E_RANGE;   // reader word indices are 32-bit
-    hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(d_status, 0, sizeof(dmx_inflate_status), s) != hipSuccess) return -(int)E_DEVICE;
+    hipLaunchKernelGGL(dmx_inflate_status_clear_kernel, dim3(1), dim3(1), 0, s, d_status);
+    if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
     // the workgroups' first-level tables: scratch from the per-device stream-ordered pool
     // (hipMallocFromPoolAsync here, hipFreeAsync on the same stream after the launch)
     const uint64_t tb = (uint64_t)(d_index ? nblk : 1) * ITAB_WORDS * 4;
@@ -974,7 +988,7 @@ extern "C" int dmx_inflate_async(const void* d_z, uint64_t zbytes, const dmx_ibl
     if (!gtab) return -(int)E_MALLOC;
     if (d_index)
         hipLaunchKernelGGL(dmx_inflate_index_kernel<false>, dim3(nblk), dim3(64), 0, s, (const uint8_t*)d_z, zbytes,
-                           d_index, (uint8_t*)d_out, out_cap, gtab, d_status);
+                           d_index, (uint8_t*)d_out, out_cap, gtab, max_len, d_status);
     else
         hipLaunchKernelGGL(dmx_inflate_stream_kernel, dim3(1), dim3(64), 0, s, (const uint8_t*)d_z, zbytes,
                            (uint8_t*)d_out, out_cap, gtab, d_status);
@@ -982,6 +996,26 @@ extern "C" int dmx_inflate_async(const void* d_z, uint64_t zbytes, const dmx_ibl
     (void)hipFreeAsync(gtab, s);   // stream-ordered: after the decode
     if (le != hipSuccess) return -(int)E_DEVICE;
     return 0;
+}
+
+extern "C" int dmx_inflate_async(const void* d_z, uint64_t zbytes, const dmx_iblock* d_index, uint32_t nblk,
+                                 void* d_out, uint64_t out_cap, dmx_inflate_status* d_status, void* stream) {
+    if (!d_z || !d_out || !d_status || (d_index && !nblk)) return -(int)E_INVAL;
+    return inflate_launch(d_z, zbytes, d_index, nblk, d_out, out_cap, IW, d_status, (hipStream_t)stream);
+}
+
+// The members of any BGZF file (include/dmx.h): the indexed decode with the format's own bound on
+// a member, then the members' CRC-32s over the decoded ranges, compared on the device.  The CRC
+// kernel ends at once after a failed decode and otherwise sets -E_CRC by compare-and-swap.
+extern "C" int dmx_inflate_members_async(const void* d_z, uint64_t zbytes, const dmx_iblock* d_index, uint32_t nblk,
+                                         void* d_out, uint64_t out_cap, const uint32_t* d_crc_want,
+                                         dmx_inflate_status* d_status, void* stream) {
+    if (!d_z || !d_out || !d_status || !d_index || !nblk) return -(int)E_INVAL;
+    if ((reinterpret_cast<uintptr_t>(d_crc_want) & 3) != 0) return -(int)E_INVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const int r = inflate_launch(d_z, zbytes, d_index, nblk, d_out, out_cap, DMX_BGZF_MAX_ISIZE, d_status, s);
+    if (r || !d_crc_want) return r;
+    return dmx_crc32_ranges_launch(d_out, out_cap, d_index, nblk, NULL, d_crc_want, d_status, s);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1243,7 +1277,7 @@ extern "C" int dmx_inflate_chained_async(const void* d_z, uint64_t zbytes, const
     if (hipMemsetAsync(d_status, 0, sizeof(dmx_inflate_status), s) != hipSuccess) return -(int)E_DEVICE;
     if (hipMemsetAsync(T, 0, 256, s) != hipSuccess) return -(int)E_DEVICE;
     hipLaunchKernelGGL(dmx_inflate_index_kernel<true>, dim3(nblk), dim3(64), 0, s, (const uint8_t*)d_z, zbytes, d_index,
-                       (uint8_t*)cells, out_cap, gtab, d_status);
+                       (uint8_t*)cells, out_cap, gtab, (uint32_t)IW, d_status);
     hipLaunchKernelGGL(dmx_cells_prep_kernel, dim3(nblk), dim3(CHAIN_WG), 0, s, d_index, cells, P, L[0], C[0], T, out_cap, d_status);
     uint32_t rounds = 2;   // pointer jumping: a chain through k blocks takes ~log2(k) + 1 rounds
     while ((1ull << (rounds - 2)) < (uint64_t)nblk && rounds < CHAIN_ROUNDS_MAX) rounds++;

@@ -386,8 +386,9 @@ int dmx_inflate_chained_async(const void* d_z, uint64_t zbytes, const dmx_iblock
 int dmx_inflate_chained_lists(const void* d_work, uint32_t* host, uint32_t n, void* stream);
 
 /* The block index of a BGZF file in host memory (DMX_F_BGZF output, or any BGZF file whose
- * members hold at most 32768 bytes of input each -- htslib's default 65280-byte blocks are out
- * of range for the one-wave-per-block decoder): walks the members by the BSIZE of their "BC"
+ * members hold at most 32768 bytes of input each, the bound of dmx_inflate_async's indexed mode
+ * -- for htslib's default 65280-byte blocks, and any member the format allows, use
+ * dmx_bgzf_index_max and dmx_inflate_members_async): walks the members by the BSIZE of their "BC"
  * FEXTRA subfield (other subfields may precede or follow it) and emits one entry per member with
  * ISIZE > 0 -- bit = first bit of its DEFLATE data, out_off = the sum of the ISIZEs before it,
  * out_len = ISIZE -- and the member's stored CRC-32 into crc[] (may be NULL); empty members, the
@@ -398,6 +399,35 @@ int dmx_inflate_chained_lists(const void* d_work, uint32_t* host, uint32_t n, vo
  * (truncated), -E_SZ (cap too small), -E_RANGE (a member with ISIZE > 32768).  Host only. */
 int dmx_bgzf_index(const uint8_t* z, uint64_t zlen, dmx_iblock* idx, uint32_t* crc, uint32_t cap, uint32_t* nblk,
                    uint64_t* out_len);
+/* The same walk with the caller's bound on a member's ISIZE: max_isize is 1..DMX_BGZF_MAX_ISIZE
+ * (else -E_RANGE), and a member with ISIZE > max_isize is -E_RANGE.  BSIZE is 16 bits, so the
+ * format itself allows no member of more than 65536 bytes, compressed or not: with
+ * DMX_BGZF_MAX_ISIZE every sound BGZF file indexes, and the entries are input for
+ * dmx_inflate_members_async.  dmx_bgzf_index is this call with 32768.  Host only. */
+#define DMX_BGZF_MAX_ISIZE 65536
+int dmx_bgzf_index_max(const uint8_t* z, uint64_t zlen, uint32_t max_isize, dmx_iblock* idx, uint32_t* crc,
+                       uint32_t cap, uint32_t* nblk, uint64_t* out_len);
+/* Inflate the nblk members (or any independently decodable entries) listed in d_index in
+ * parallel, one wave each, into d_out + out_off: dmx_inflate_async's indexed mode with out_len up
+ * to DMX_BGZF_MAX_ISIZE, same statuses, -E_RANGE for an entry outside the stream or the output or
+ * with out_len > 65536.  d_crc_want != NULL (nblk words, 4-byte aligned: the members' stored
+ * CRC-32s as dmx_bgzf_index_max gives them): the CRC-32 of every decoded range is then computed on
+ * the same stream (dmx_crc32_ranges_async's kernel) and compared on the device; a member that
+ * differs sets d_status->status = -E_CRC unless a status is already there (a decode error stays,
+ * and after one the CRC pass does nothing).  Takes no context; the table scratch comes from the
+ * pool dmx_inflate_async uses.  No host synchronisation (graph-capturable where the runtime
+ * captures the pool's allocation).  Returns 0 or -E_* as dmx_inflate_async. */
+int dmx_inflate_members_async(const void* d_z, uint64_t zbytes, const dmx_iblock* d_index, uint32_t nblk,
+                              void* d_out, uint64_t out_cap, const uint32_t* d_crc_want,
+                              dmx_inflate_status* d_status, void* stream);
+/* Host-buffer convenience (H2D, index, decode, D2H) on the cached per-device context
+ * dmx_encode_host uses: any BGZF file z[0..zlen) into out.  *out_len receives the decoded length
+ * (the sum of the ISIZEs) whenever the file indexes, also when out_cap is too small (-E_SZ,
+ * nothing decoded).  verify != 0 checks every member's CRC-32 on the device (-E_CRC).  An empty
+ * file, or one of empty members only, gives 0 bytes and 0.  Returns 0, the index walk's status,
+ * or the decode's device status. */
+int dmx_bgzf_decode_host(const uint8_t* z, uint64_t zlen, uint8_t* out, uint64_t out_cap, uint64_t* out_len,
+                         int verify);
 
 /* Introspection of the last encode of ctx (tests / fd_stats): per-block token
  * counts and the token stream (t = byte | dist << 9 | len),
@@ -461,6 +491,19 @@ int dmx_crc32_async(dmx_ctx* ctx, const void* d_in, uint64_t n, uint32_t* d_crc,
  * need no ordering against other work of the context.  Reads whole 16-byte groups as
  * dmx_crc32_async does.  -E_SZ when there are 2^31 blocks or more.  Returns 0 or -E_*. */
 int dmx_crc32_blocks_async(dmx_ctx* ctx, const void* d_in, uint64_t n, int32_t sw, uint32_t* d_crc, void* stream);
+/* Enqueue the CRC-32 of the nblk ranges of d_in[0..n) that the device index lists (bit is not
+ * read): d_crc[k] (4-byte aligned, nblk words) receives the finished value of
+ * d_in[out_off_k, out_off_k + out_len_k).  out_off is any byte offset, out_len 0..65536
+ * (DMX_BGZF_MAX_ISIZE; 0 gives 0); the ranges may come in any order and may overlap.  An entry
+ * with out_len > 65536 or out_off + out_len > n writes nothing to its word and, when d_status is
+ * not NULL, sets d_status->status = -E_RANGE unless a status is already there; the other words are
+ * written all the same.  d_status is the caller's to clear.  Takes no context (the current
+ * device); one launch, no scratch, no allocation, no host synchronisation (graph-capturable).
+ * Reads whole 16-byte groups around the ends of every range as dmx_crc32_async does: up to 15
+ * bytes before and after it, inside the aligned groups that hold its first and last byte.
+ * Returns 0 or -E_*. */
+int dmx_crc32_ranges_async(const void* d_in, uint64_t n, const dmx_iblock* d_index, uint32_t nblk, uint32_t* d_crc,
+                           dmx_inflate_status* d_status, void* stream);
 /* CRC-32 combine: crc of A||B from crc(A), crc(B), len(B).  Host only. */
 uint32_t dmx_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
 /* The CRC kernel's geometry (tests): bytes per workgroup span and per lane slice. */
