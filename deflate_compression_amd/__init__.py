@@ -12,6 +12,7 @@ include/dmx.h).  This module is a thin ctypes layer:
                                                           bgzf=True: BGZF, a gzip member per block)
     bgzf_index(z) / inflate_bgzf_gpu(z)                   a BGZF file's members, decoded in parallel on the GPU
     decompress_bgzf(z) -> bytes                           the same from and to host buffers (any BGZF file)
+    bgzf_index_gpu(zt) / inflate_bgzf_tensor(zt)          a BGZF file in device memory: indexed and decoded where it lies
     Encoder                                               device-resident encodes
 
 There is no CPU fallback: if libdmx.so is missing the import of this module fails,
@@ -26,7 +27,7 @@ import struct
 __all__ = [
     "DeflateError", "Opts", "Result", "Encoder", "lib", "compress", "deflate_compress",
     "deflate_decompress", "max_compressed", "adler32_combine", "gen_text", "gen_random",
-    "COMPRESS_STATS", "E", "DMX_F_HEADER", "DMX_F_TRAILER", "DMX_F_FINAL", "DMX_ZLIB", "DMX_F_LAZY", "DMX_F_EXACT_SORT", "DMX_F_SPLIT", "DMX_F_DICT", "DMX_F_STORE_CHECK", "DMX_F_DEEP", "DMX_F_GZIP", "DMX_GZIP", "DMX_F_BGZF", "DMX_BGZF", "crc32_combine", "crc32_geometry", "bgzf_index", "inflate_bgzf_gpu", "decompress_bgzf", "crc32_ranges", "DMX_BGZF_MAX_ISIZE", "inflate_gpu", "inflate_gpu_chained", "ref_estimates",
+    "COMPRESS_STATS", "E", "DMX_F_HEADER", "DMX_F_TRAILER", "DMX_F_FINAL", "DMX_ZLIB", "DMX_F_LAZY", "DMX_F_EXACT_SORT", "DMX_F_SPLIT", "DMX_F_DICT", "DMX_F_STORE_CHECK", "DMX_F_DEEP", "DMX_F_GZIP", "DMX_GZIP", "DMX_F_BGZF", "DMX_BGZF", "crc32_combine", "crc32_geometry", "bgzf_index", "inflate_bgzf_gpu", "decompress_bgzf", "bgzf_index_gpu", "inflate_bgzf_tensor", "crc32_ranges", "DMX_BGZF_MAX_ISIZE", "inflate_gpu", "inflate_gpu_chained", "ref_estimates",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -131,6 +132,10 @@ def lib() -> ctypes.CDLL:
         "dmx_bgzf_index_max": ([vp, u64, u32, vp, vp, u32, u32p, ctypes.POINTER(u64)], ctypes.c_int),
         "dmx_bgzf_decode_host": ([vp, u64, vp, u64, ctypes.POINTER(u64), ctypes.c_int], ctypes.c_int),
         "dmx_crc32_ranges_async": ([vp, u64, vp, u32, vp, vp, vp], ctypes.c_int),
+        "dmx_bgzf_index_work": ([u64, u32], u64),
+        "dmx_bgzf_index_geometry": ([u32p], None),
+        "dmx_bgzf_index_async": ([vp, u64, u32, vp, vp, u32, vp, u64, vp, vp], ctypes.c_int),
+        "dmx_bgzf_decode_device": ([vp, u64, vp, u64, ctypes.POINTER(u64), ctypes.c_int, vp], ctypes.c_int),
         "dmx_inflate_members_async": ([vp, u64, vp, u32, vp, u64, vp, vp, vp], ctypes.c_int),
         "dmx_crc32_combine": ([u32, u32, u64], u32),
         "dmx_crc32_geometry": ([u32p, u32p], None),
@@ -378,6 +383,78 @@ def decompress_bgzf(z, verify: bool = True) -> bytes:
     _check(L.dmx_bgzf_decode_host(p, n, out, olen.value, ctypes.byref(olen), 1 if verify else 0), "dmx_bgzf_decode_host")
     del keep
     return out.raw[:olen.value]
+
+
+def bgzf_index_gpu(zt, max_member: int = DMX_BGZF_MAX_ISIZE, cap: int | None = None, stream=None):
+    """The members of a BGZF file in device memory, found on the device (dmx_bgzf_index_async): zt is
+    a uint8 CUDA tensor, any alignment.  Returns (index, crcs, nblk, total) as dmx_bgzf_index_max
+    gives them for the same bytes -- index a uint8 CUDA tensor of nblk x 24 B dmx_iblock records,
+    crcs an int32 CUDA tensor of the members' stored CRC-32s (view as uint32 on the host), input
+    for dmx_inflate_members_async -- and raises DeflateError with the walk's status for a file that
+    does not index.  cap: room for that many entries (-E_SZ where the file has more); by default
+    as many as the work buffer has candidates.  The work buffer holds zt.numel() // 256 + 1024
+    candidates; a file whose data spells more member headers than that is indexed once more with
+    the number the first pass reports.  Synchronises the stream to read the 24-byte record."""
+    import numpy as np
+    import torch
+    L = lib()
+    dev = zt.device
+    n = zt.numel()
+    if n and (zt.dtype != torch.uint8 or not zt.is_cuda or not zt.is_contiguous()):
+        raise ValueError("bgzf_index_gpu takes a contiguous uint8 CUDA tensor")
+    max_cand = n // 256 + 1024
+    with torch.cuda.device(dev):
+        s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        for attempt in (0, 1):
+            room = max_cand if cap is None else cap
+            wb = int(L.dmx_bgzf_index_work(n, max_cand))
+            work = torch.empty(wb, dtype=torch.uint8, device=dev)
+            index = torch.empty(max(room, 1) * 24, dtype=torch.uint8, device=dev)
+            crcs = torch.empty(max(room, 1), dtype=torch.int32, device=dev)
+            st = torch.empty(24, dtype=torch.uint8, device=dev)
+            _check(L.dmx_bgzf_index_async(ctypes.c_void_p(zt.data_ptr() if n else 0), n, max_member,
+                                          ctypes.c_void_p(index.data_ptr()), ctypes.c_void_p(crcs.data_ptr()), room,
+                                          ctypes.c_void_p(work.data_ptr()), wb, ctypes.c_void_p(st.data_ptr()),
+                                          ctypes.c_void_p(s)), "dmx_bgzf_index_async")
+            if stream is not None:
+                torch.cuda.synchronize(dev)
+            h = st.cpu().numpy()
+            status, nblk, ncand = int(h[:4].view(np.int32)[0]), int(h[4:8].view(np.uint32)[0]), int(h[16:20].view(np.uint32)[0])
+            total = int(h[8:16].view(np.uint64)[0])
+            if status == -E["E_SZ"] and nblk == 0 and ncand > max_cand and attempt == 0:
+                max_cand = ncand
+                continue
+            break
+    if status:
+        raise DeflateError(status, "dmx_bgzf_index_async")
+    return index[:nblk * 24], crcs[:nblk], nblk, total
+
+
+def inflate_bgzf_tensor(zt, verify: bool = True):
+    """Inflate a BGZF file that lies in device memory (a uint8 CUDA tensor, any alignment) into a new
+    uint8 CUDA tensor on the same device, without a copy of the file to the host
+    (dmx_bgzf_decode_device): the device index, then every member decoded in parallel and, with
+    `verify`, its CRC-32 checked on the device (DeflateError(-E_CRC)).  Two calls, as
+    decompress_bgzf: the first for the decoded length.  An empty file, or one of empty members
+    only, gives an empty tensor."""
+    import torch
+    L = lib()
+    dev = zt.device
+    n = zt.numel()
+    if n and (zt.dtype != torch.uint8 or not zt.is_cuda or not zt.is_contiguous()):
+        raise ValueError("inflate_bgzf_tensor takes a contiguous uint8 CUDA tensor")
+    olen = ctypes.c_uint64(0)
+    with torch.cuda.device(dev):
+        s = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        zp = ctypes.c_void_p(zt.data_ptr() if n else 0)
+        r = L.dmx_bgzf_decode_device(zp, n, None, 0, ctypes.byref(olen), 1 if verify else 0, s)   # the decoded length
+        if r != -E["E_SZ"]:
+            _check(r, "dmx_bgzf_decode_device")
+            return torch.empty(0, dtype=torch.uint8, device=dev)
+        out = torch.empty(olen.value, dtype=torch.uint8, device=dev)
+        _check(L.dmx_bgzf_decode_device(zp, n, ctypes.c_void_p(out.data_ptr()), olen.value, ctypes.byref(olen),
+                                        1 if verify else 0, s), "dmx_bgzf_decode_device")
+    return out
 
 
 def inflate_gpu_chained(z, out_cap: int, index, nblk: int, stream=None, work=None):

@@ -100,6 +100,9 @@ DMX_HIDDEN int hip_fail(hipError_t e, const char* what);
 DMX_HIDDEN int dmx_crc32_ranges_launch(const void* d_in, uint64_t n, const dmx_iblock* d_index, uint32_t nblk,
                                        uint32_t* d_crc, const uint32_t* d_want, dmx_inflate_status* d_status,
                                        hipStream_t s);
+// `bytes` of device scratch from the inflate's per-device stream-ordered pool (dmx_inflate_dev.hip),
+// allocated on s; NULL when that fails.  The caller frees it with hipFreeAsync on the same stream.
+DMX_HIDDEN void* dmx_itab_scratch(hipStream_t s, uint64_t bytes);
 // the fd pipeline's buffers of a context (dmx_fd.cpp), freed with the context
 DMX_HIDDEN void fdp_free(FdPipe* P);
 

@@ -965,6 +965,8 @@ static uint32_t* itab_scratch(hipStream_t s, uint64_t bytes) {
         return nullptr;
     return (uint32_t*)p;
 }
+// the same pool for the scratch of dmx_bgzf_decode_device (dmx_bgzf_index.hip); hipFreeAsync on s frees it
+void* dmx_itab_scratch(hipStream_t s, uint64_t bytes) { return itab_scratch(s, bytes); }
 
 // The status record's reset.  A kernel, not hipMemsetAsync: captured into a graph (ROCm 7.2), the
 // 16-byte memset node wrote zeros on the first replay only and other bytes on every later one.

@@ -396,14 +396,16 @@ int dmx_inflate_chained_lists(const void* d_work, uint32_t* host, uint32_t n, vo
  * is too small), *out_len the total of the ISIZEs.  The entries are input for dmx_inflate_async
  * once copied to the device (a member may hold several DEFLATE blocks: the decoder runs to
  * BFINAL).  Returns 0, -E_ZHEAD (a member is not gzip / deflate or has no BC subfield), -E_LEN
- * (truncated), -E_SZ (cap too small), -E_RANGE (a member with ISIZE > 32768).  Host only. */
+ * (truncated), -E_SZ (cap too small), -E_RANGE (a member with ISIZE > 32768).  Host only (a file
+ * in device memory: dmx_bgzf_index_async). */
 int dmx_bgzf_index(const uint8_t* z, uint64_t zlen, dmx_iblock* idx, uint32_t* crc, uint32_t cap, uint32_t* nblk,
                    uint64_t* out_len);
 /* The same walk with the caller's bound on a member's ISIZE: max_isize is 1..DMX_BGZF_MAX_ISIZE
  * (else -E_RANGE), and a member with ISIZE > max_isize is -E_RANGE.  BSIZE is 16 bits, so the
  * format itself allows no member of more than 65536 bytes, compressed or not: with
  * DMX_BGZF_MAX_ISIZE every sound BGZF file indexes, and the entries are input for
- * dmx_inflate_members_async.  dmx_bgzf_index is this call with 32768.  Host only. */
+ * dmx_inflate_members_async.  dmx_bgzf_index is this call with 32768.  Host only; it is the
+ * specification of dmx_bgzf_index_async, which does the same on a file in device memory. */
 #define DMX_BGZF_MAX_ISIZE 65536
 int dmx_bgzf_index_max(const uint8_t* z, uint64_t zlen, uint32_t max_isize, dmx_iblock* idx, uint32_t* crc,
                        uint32_t cap, uint32_t* nblk, uint64_t* out_len);
@@ -420,6 +422,53 @@ int dmx_bgzf_index_max(const uint8_t* z, uint64_t zlen, uint32_t max_isize, dmx_
 int dmx_inflate_members_async(const void* d_z, uint64_t zbytes, const dmx_iblock* d_index, uint32_t nblk,
                               void* d_out, uint64_t out_cap, const uint32_t* d_crc_want,
                               dmx_inflate_status* d_status, void* stream);
+/* The same index for a BGZF file that lies in device memory, built on the device
+ * (csrc/dmx_bgzf_index.hip): every position of the file that parses as a member is
+ * a candidate, and pointer doubling over the candidates' BSIZE links finds the chain that starts
+ * at offset 0 -- the members of the host walk.  For the same bytes and max_isize the record and
+ * the output equal dmx_bgzf_index_max's: status (0, -E_ZHEAD, -E_LEN, -E_RANGE, -E_SZ when cap is
+ * too small, then with the first cap entries written and the full nblk and out_len), the entries
+ * (bit, out_off, out_len, reserved = 0) into d_index (8-byte aligned; NULL only with cap 0) and
+ * the members' stored CRC-32s into d_crc (4-byte aligned, or NULL), also on truncated and corrupt
+ * files and on files whose data holds bytes that look like members.  The one difference: d_work
+ * (256-byte aligned, work_bytes >= dmx_bgzf_index_work(zbytes, 1)) holds a candidate per parsing
+ * position, and a file with more of them than work_bytes has room for gives status -E_SZ with
+ * nblk = 0, out_len = 0 and ncand = the number needed: call again with
+ * dmx_bgzf_index_work(zbytes, ncand) bytes.  A sound file has at most zbytes / 26 + 1 members,
+ * and about as many candidates.  d_z may have any alignment; whole 16-byte aligned groups are
+ * loaded as in dmx_crc32_async: up to 15 bytes before d_z and after d_z + zbytes, inside the
+ * groups that hold the first and the last byte, are read and never looked at.  Takes no context
+ * (the current device).  The number of launches (5 + ceil(log2(bound + 1)), bound = the smaller of
+ * the candidates d_work holds and zbytes / 26 + 1) follows from the arguments alone: no
+ * allocation, no host synchronisation, a linear chain under graph capture; the record is reset by
+ * a kernel.  Returns before any device call: -E_INVAL (d_z NULL with zbytes > 0, d_status or d_work
+ * NULL, d_index NULL with cap > 0, d_index or d_status not 8-byte, d_crc not 4-byte, d_work not
+ * 256-byte aligned, work_bytes too small), -E_RANGE (max_isize outside 1..DMX_BGZF_MAX_ISIZE,
+ * zbytes > 0xFFFFFFF0: the decoder's own bound); else 0 or -E_DEVICE. */
+typedef struct {
+    int32_t status;    /* 0 or -E_*: dmx_bgzf_index_max's status for the same bytes */
+    uint32_t nblk;     /* members with ISIZE > 0 (also when cap is too small); 0 after any other error */
+    uint64_t out_len;  /* sum of the ISIZEs; 0 after an error other than -E_SZ for cap */
+    uint32_t ncand;    /* positions that parsed as a member (the capacity the work buffer needed) */
+    uint32_t reserved;
+} dmx_bgzf_index_status;
+/* Bytes of d_work for a file of zbytes with room for max_cand candidates (a multiple of 256). */
+uint64_t dmx_bgzf_index_work(uint64_t zbytes, uint32_t max_cand);
+/* The scan's geometry (tests): bytes of aligned 16-byte groups per scan tile (a workgroup). */
+void dmx_bgzf_index_geometry(uint32_t* tile);
+int dmx_bgzf_index_async(const void* d_z, uint64_t zbytes, uint32_t max_isize, dmx_iblock* d_index, uint32_t* d_crc,
+                         uint32_t cap, void* d_work, uint64_t work_bytes, dmx_bgzf_index_status* d_status, void* stream);
+/* Any BGZF file in device memory into d_out, device to device: dmx_bgzf_index_async with
+ * DMX_BGZF_MAX_ISIZE into scratch from the pool dmx_inflate_async uses (room for zbytes / 256 + 1024
+ * candidates; once more with the number needed where the file has more), one 24-byte copy of its
+ * record to the host -- the call's one synchronisation before the decode: the member count sizes
+ * the decode's grid and table scratch -- then dmx_inflate_members_async (verify != 0: with the
+ * members' CRC-32s, -E_CRC) and its status.  *out_len receives the decoded length whenever the
+ * file indexes, also when out_cap is too small (-E_SZ, nothing decoded, d_out untouched).  An
+ * empty file, or one of empty members only, gives 0 bytes and 0.  Returns 0, -E_INVAL / -E_RANGE
+ * for the arguments (before any device call), the index's status, or the decode's. */
+int dmx_bgzf_decode_device(const void* d_z, uint64_t zbytes, void* d_out, uint64_t out_cap, uint64_t* out_len,
+                           int verify, void* stream);
 /* Host-buffer convenience (H2D, index, decode, D2H) on the cached per-device context
  * dmx_encode_host uses: any BGZF file z[0..zlen) into out.  *out_len receives the decoded length
  * (the sum of the ISIZEs) whenever the file indexes, also when out_cap is too small (-E_SZ,
