@@ -13,6 +13,7 @@ include/dmx.h).  This module is a thin ctypes layer:
     bgzf_index(z) / inflate_bgzf_gpu(z)                   a BGZF file's members, decoded in parallel on the GPU
     decompress_bgzf(z) -> bytes                           the same from and to host buffers (any BGZF file)
     bgzf_index_gpu(zt) / inflate_bgzf_tensor(zt)          a BGZF file in device memory: indexed and decoded where it lies
+    bgzf_read_ranges(zt, ranges) / bgzf_pread(zt, off, n) byte ranges of such a file: only the members they touch are decoded
     Encoder                                               device-resident encodes
 
 There is no CPU fallback: if libdmx.so is missing the import of this module fails,
@@ -28,6 +29,8 @@ __all__ = [
     "DeflateError", "Opts", "Result", "Encoder", "lib", "compress", "deflate_compress",
     "deflate_decompress", "max_compressed", "adler32_combine", "gen_text", "gen_random",
     "COMPRESS_STATS", "E", "DMX_F_HEADER", "DMX_F_TRAILER", "DMX_F_FINAL", "DMX_ZLIB", "DMX_F_LAZY", "DMX_F_EXACT_SORT", "DMX_F_SPLIT", "DMX_F_DICT", "DMX_F_STORE_CHECK", "DMX_F_DEEP", "DMX_F_GZIP", "DMX_GZIP", "DMX_F_BGZF", "DMX_BGZF", "crc32_combine", "crc32_geometry", "bgzf_index", "inflate_bgzf_gpu", "decompress_bgzf", "bgzf_index_gpu", "inflate_bgzf_tensor", "crc32_ranges", "DMX_BGZF_MAX_ISIZE", "inflate_gpu", "inflate_gpu_chained", "ref_estimates",
+    "bgzf_read_ranges", "bgzf_pread", "bgzf_voffset", "bgzf_read_ranges_async", "ranges_geometry", "BRange", "RangesStatus",
+    "DMX_RANGES_VIRTUAL",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -48,6 +51,7 @@ DMX_GZIP = DMX_ZLIB | DMX_F_GZIP
 DMX_F_BGZF = 1024
 DMX_BGZF = DMX_F_BGZF | DMX_F_FINAL
 DMX_BGZF_MAX_ISIZE = 65536
+DMX_RANGES_VIRTUAL = 1
 _M = 1 << 24
 # src/include/global_errors.h:24-35 and src/include/deflate_errors.h:9-22
 E = {
@@ -87,6 +91,17 @@ class FdStats(ctypes.Structure):
     _fields_ = [("chunks", ctypes.c_uint64), ("bytes_in", ctypes.c_uint64), ("bytes_out", ctypes.c_uint64),
                 ("wall_ms", ctypes.c_double), ("read_ms", ctypes.c_double), ("h2d_ms", ctypes.c_double),
                 ("encode_ms", ctypes.c_double), ("d2h_ms", ctypes.c_double), ("write_ms", ctypes.c_double)]
+
+
+class BRange(ctypes.Structure):
+    """dmx_brange: one (offset, length) request of dmx_bgzf_read_ranges_async"""
+    _fields_ = [("off", ctypes.c_uint64), ("len", ctypes.c_uint64)]
+
+
+class RangesStatus(ctypes.Structure):
+    """dmx_bgzf_ranges_status: the 32-byte device record of dmx_bgzf_read_ranges_async"""
+    _fields_ = [("status", ctypes.c_int32), ("nmembers", ctypes.c_uint32), ("out_len", ctypes.c_uint64),
+                ("scratch_len", ctypes.c_uint64), ("bad", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
 class _StringLen(ctypes.Structure):
@@ -137,6 +152,12 @@ def lib() -> ctypes.CDLL:
         "dmx_bgzf_index_async": ([vp, u64, u32, vp, vp, u32, vp, u64, vp, vp], ctypes.c_int),
         "dmx_bgzf_decode_device": ([vp, u64, vp, u64, ctypes.POINTER(u64), ctypes.c_int, vp], ctypes.c_int),
         "dmx_inflate_members_async": ([vp, u64, vp, u32, vp, u64, vp, vp, vp], ctypes.c_int),
+        "dmx_bgzf_ranges_work": ([u32, u32, u32, u64], u64),
+        "dmx_bgzf_ranges_geometry": ([u32p, u32p], None),
+        "dmx_bgzf_read_ranges_async": ([vp, u64, vp, vp, u32, vp, u32, u32, vp, u64, vp, u32, u64, vp, u64, vp, vp],
+                                       ctypes.c_int),
+        "dmx_bgzf_read_device": ([vp, u64, vp, vp, u32, vp, u32, u32, vp, u64, vp, ctypes.POINTER(u64), ctypes.c_int, vp],
+                                 ctypes.c_int),
         "dmx_crc32_combine": ([u32, u32, u64], u32),
         "dmx_crc32_geometry": ([u32p, u32p], None),
         "dmx_fd_last_stats": ([ctypes.POINTER(FdStats)], ctypes.c_int),
@@ -454,6 +475,142 @@ def inflate_bgzf_tensor(zt, verify: bool = True):
         out = torch.empty(olen.value, dtype=torch.uint8, device=dev)
         _check(L.dmx_bgzf_decode_device(zp, n, ctypes.c_void_p(out.data_ptr()), olen.value, ctypes.byref(olen),
                                         1 if verify else 0, s), "dmx_bgzf_decode_device")
+    return out
+
+
+def bgzf_voffset(member_off: int, within: int) -> int:
+    """The BGZF virtual offset of byte `within` of the data of the member at file offset member_off
+    (what .bai / .tbi indexes store): member_off << 16 | within."""
+    if not (0 <= within < 65536 and 0 <= member_off < 1 << 48):
+        raise ValueError("a virtual offset holds a 48-bit file offset and a 16-bit offset in the member")
+    return (member_off << 16) | within
+
+
+def ranges_geometry() -> tuple[int, int]:
+    """(members, ranges) per scan tile of dmx_bgzf_read_ranges_async (tests straddle them)"""
+    t, r = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    lib().dmx_bgzf_ranges_geometry(ctypes.byref(t), ctypes.byref(r))
+    return int(t.value), int(r.value)
+
+
+def _ranges_tensor(ranges, dev):
+    """ranges as an int64 CUDA tensor of shape (n, 2): the bits of n dmx_brange records"""
+    import numpy as np
+    import torch
+    if isinstance(ranges, torch.Tensor):
+        if ranges.dim() != 2 or ranges.shape[1] != 2 or ranges.dtype not in (torch.int64, torch.uint64):
+            raise ValueError("ranges is an (n, 2) int64 / uint64 array of (off, len)")
+        return ranges.view(torch.int64).contiguous().to(dev)
+    a = np.asarray(ranges, dtype=np.uint64) if not isinstance(ranges, np.ndarray) else ranges
+    if a.size == 0:
+        a = a.reshape(0, 2)
+    if a.ndim != 2 or a.shape[1] != 2 or a.dtype not in (np.int64, np.uint64):
+        raise ValueError("ranges is an (n, 2) int64 / uint64 array of (off, len)")
+    return torch.from_numpy(np.ascontiguousarray(a).view(np.int64).copy()).to(dev)
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
+
+
+def bgzf_read_ranges_async(zt, index, crcs, nblk: int, ranges, nranges: int, flags: int, out, out_cap: int, offsets,
+                           max_members: int, scratch_bytes: int, work, status, stream=None) -> int:
+    """dmx_bgzf_read_ranges_async on caller-owned CUDA tensors, enqueued on `stream` (the current
+    one by default) with no synchronisation, so it can be captured into a graph: index / crcs / nblk
+    as bgzf_index_gpu returns them (crcs None: no verification), ranges an (n, 2) int64 tensor,
+    offsets an int64 tensor of nranges + 1, work a uint8 tensor of lib().dmx_bgzf_ranges_work(...)
+    bytes (256-byte aligned), status a 32-byte uint8 tensor (RangesStatus).  Returns the call's own
+    return code; the outcome is in the record."""
+    import torch
+    dev = work.device
+    with torch.cuda.device(dev):
+        s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        return lib().dmx_bgzf_read_ranges_async(_ptr(zt), zt.numel(), _ptr(index), _ptr(crcs), nblk, _ptr(ranges), nranges,
+                                                flags, _ptr(out), out_cap, ctypes.c_void_p(offsets.data_ptr()), max_members,
+                                                scratch_bytes, ctypes.c_void_p(work.data_ptr()), work.numel(),
+                                                ctypes.c_void_p(status.data_ptr()), ctypes.c_void_p(s))
+
+
+def _ranges_record(status) -> RangesStatus:
+    """the record of a 32-byte status tensor (synchronises)"""
+    return RangesStatus.from_buffer_copy(status.cpu().numpy().tobytes())
+
+
+def bgzf_read_ranges(zt, ranges, index=None, virtual: bool = False, verify: bool = True, info: dict | None = None):
+    """Read many ranges of the decoded bytes of a BGZF file that lies in device memory
+    (dmx_bgzf_read_ranges_async): zt is a contiguous uint8 CUDA tensor, ranges an (n, 2) int64 /
+    uint64 array or CUDA tensor of (off, len) -- clipped as pread clips, in any order, overlapping
+    or repeated -- or with `virtual` of (BGZF virtual offset, len), see bgzf_voffset.  index: the
+    tuple bgzf_index_gpu(zt) returns, built here when None (pass it when reading more than once).
+    Only the members the ranges touch are decoded, once each, and with `verify` their CRC-32s are
+    checked on the device.  Returns (out, offsets): the bytes packed back to back as a uint8 CUDA
+    tensor and an int64 CUDA tensor of n + 1 with range q at out[offsets[q]:offsets[q + 1]].
+    Raises DeflateError with the record's status; for -E_RANGE the message names the bad range.
+    info: a dict that receives nmembers, scratch_len and out_len of the record.  Two enqueues with
+    one synchronisation between them: the first plans, its record sizes the second."""
+    import torch
+    L = lib()
+    dev = zt.device
+    if zt.numel() and (zt.dtype != torch.uint8 or not zt.is_cuda or not zt.is_contiguous()):
+        raise ValueError("bgzf_read_ranges takes a contiguous uint8 CUDA tensor")
+    if index is None:
+        index = bgzf_index_gpu(zt)
+    ix, crcs, nblk, _ = index
+    rt = _ranges_tensor(ranges, dev)
+    n = rt.shape[0]
+    flags = DMX_RANGES_VIRTUAL if virtual else 0
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    st = torch.empty(32, dtype=torch.uint8, device=dev)
+    out = torch.empty(0, dtype=torch.uint8, device=dev)
+    want = crcs if verify else None
+    members, scratch = 0, 0
+    for attempt in (0, 1):
+        work = torch.empty(int(L.dmx_bgzf_ranges_work(nblk, n, members, scratch)), dtype=torch.uint8, device=dev)
+        _check(bgzf_read_ranges_async(zt, ix, want, nblk, rt, n, flags, out, out.numel(), offsets, members, scratch, work, st),
+               "dmx_bgzf_read_ranges_async")
+        rec = _ranges_record(st)
+        if attempt == 0 and rec.status == -E["E_SZ"]:   # planned: size the real call by the record
+            members, scratch = rec.nmembers, rec.scratch_len
+            out = torch.empty(rec.out_len, dtype=torch.uint8, device=dev)
+            continue
+        break
+    if info is not None:
+        info.update(nmembers=rec.nmembers, scratch_len=rec.scratch_len, out_len=rec.out_len)
+    if rec.status == -E["E_RANGE"]:
+        bad = rt[rec.bad].cpu().numpy().view("uint64")
+        raise DeflateError(rec.status, f"bgzf_read_ranges: range {rec.bad} (virtual offset {int(bad[0]):#x}, len {int(bad[1])})")
+    if rec.status:
+        raise DeflateError(rec.status, "bgzf_read_ranges")
+    return out, offsets
+
+
+def bgzf_pread(zt, off: int, n: int, index=None, verify: bool = True):
+    """Bytes [off, off + n) of the decoded bytes of a BGZF file in device memory, clipped at its end
+    as pread clips (dmx_bgzf_read_device): a uint8 CUDA tensor.  index: the tuple bgzf_index_gpu(zt)
+    returns, built here when None.  Two calls, as inflate_bgzf_tensor: the first for the length."""
+    import numpy as np
+    import torch
+    L = lib()
+    dev = zt.device
+    if zt.numel() and (zt.dtype != torch.uint8 or not zt.is_cuda or not zt.is_contiguous()):
+        raise ValueError("bgzf_pread takes a contiguous uint8 CUDA tensor")
+    if index is None:
+        index = bgzf_index_gpu(zt)
+    ix, crcs, nblk, _ = index
+    rt = _ranges_tensor(np.array([[off, n]], dtype=np.uint64), dev)
+    offsets = torch.empty(2, dtype=torch.int64, device=dev)
+    olen = ctypes.c_uint64(0)
+    out = torch.empty(0, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        s = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        for attempt in (0, 1):
+            r = L.dmx_bgzf_read_device(_ptr(zt), zt.numel(), _ptr(ix), _ptr(crcs), nblk, _ptr(rt), 1, 0, _ptr(out), out.numel(),
+                                       ctypes.c_void_p(offsets.data_ptr()), ctypes.byref(olen), 1 if verify else 0, s)
+            if attempt == 0 and r == -E["E_SZ"]:
+                out = torch.empty(olen.value, dtype=torch.uint8, device=dev)
+                continue
+            break
+    _check(r, "dmx_bgzf_read_device")
     return out
 
 

@@ -103,6 +103,13 @@ DMX_HIDDEN int dmx_crc32_ranges_launch(const void* d_in, uint64_t n, const dmx_i
 // `bytes` of device scratch from the inflate's per-device stream-ordered pool (dmx_inflate_dev.hip),
 // allocated on s; NULL when that fails.  The caller frees it with hipFreeAsync on the same stream.
 DMX_HIDDEN void* dmx_itab_scratch(hipStream_t s, uint64_t bytes);
+// The counted form of the indexed decode (dmx_inflate_dev.hip) for dmx_bgzf_read_ranges_async: a
+// grid of `slots` workgroups over d_index, of which those at or past *d_count leave at once; d_gtab
+// holds dmx_itab_bytes(slots) bytes of first-level tables.  d_status is the caller's to reset.
+DMX_HIDDEN uint64_t dmx_itab_bytes(uint32_t slots);
+DMX_HIDDEN int dmx_inflate_counted_launch(const void* d_z, uint64_t zbytes, const dmx_iblock* d_index, uint32_t slots,
+                                          const uint32_t* d_count, void* d_out, uint64_t out_cap, void* d_gtab,
+                                          dmx_inflate_status* d_status, hipStream_t s);
 // the fd pipeline's buffers of a context (dmx_fd.cpp), freed with the context
 DMX_HIDDEN void fdp_free(FdPipe* P);
 

@@ -826,12 +826,17 @@ __device__ __forceinline__ int iblock(InfLDS<W, typename std::conditional<CELL, 
 // distance below IW, and the chained lists 16-bit offsets), DMX_BGZF_MAX_ISIZE for the members of
 // dmx_inflate_members_async.  Nothing below depends on it (the audit): positions
 // are 32-bit, the ring index is a mask, and sources older than the ring come from d_out.
-template <bool CELL>
+// COUNTED (dmx_bgzf_read_ranges_async): the grid is a capacity the host knows, the number of entries
+// the word *count that the planning kernels left in device memory.  A workgroup at or past it leaves
+// at once, a uniform exit on one scalar load; without COUNTED count is not read (NULL).
+template <bool CELL, bool COUNTED = false>
 __global__ __launch_bounds__(64) void dmx_inflate_index_kernel(const uint8_t* __restrict__ z, uint64_t zbytes,
                                                                const dmx_iblock* __restrict__ index,
                                                                uint8_t* __restrict__ out, uint64_t out_cap,
                                                                uint32_t* __restrict__ gtab, uint32_t max_len,
-                                                               dmx_inflate_status* __restrict__ st) {
+                                                               dmx_inflate_status* __restrict__ st,
+                                                               const uint32_t* __restrict__ count) {
+    if (COUNTED && blockIdx.x >= *count) return;
     // bytes: an 8 KiB ring, 10 KiB of LDS; cells: 4 096 cells, the same 10 KiB.  12 workgroups
     // per CU (151 VGPRs: 3 waves per SIMD), so 3 072 blocks decode at once
     constexpr uint32_t WR = CELL ? IWC : IWX;
@@ -990,7 +995,7 @@ static int inflate_launch(const void* d_z, uint64_t zbytes, const dmx_iblock* d_
     if (!gtab) return -(int)E_MALLOC;
     if (d_index)
         hipLaunchKernelGGL(dmx_inflate_index_kernel<false>, dim3(nblk), dim3(64), 0, s, (const uint8_t*)d_z, zbytes,
-                           d_index, (uint8_t*)d_out, out_cap, gtab, max_len, d_status);
+                           d_index, (uint8_t*)d_out, out_cap, gtab, max_len, d_status, (const uint32_t*)nullptr);
     else
         hipLaunchKernelGGL(dmx_inflate_stream_kernel, dim3(1), dim3(64), 0, s, (const uint8_t*)d_z, zbytes,
                            (uint8_t*)d_out, out_cap, gtab, d_status);
@@ -1004,6 +1009,18 @@ extern "C" int dmx_inflate_async(const void* d_z, uint64_t zbytes, const dmx_ibl
                                  void* d_out, uint64_t out_cap, dmx_inflate_status* d_status, void* stream) {
     if (!d_z || !d_out || !d_status || (d_index && !nblk)) return -(int)E_INVAL;
     return inflate_launch(d_z, zbytes, d_index, nblk, d_out, out_cap, IW, d_status, (hipStream_t)stream);
+}
+
+uint64_t dmx_itab_bytes(uint32_t slots) { return (uint64_t)slots * ITAB_WORDS * 4; }
+
+int dmx_inflate_counted_launch(const void* d_z, uint64_t zbytes, const dmx_iblock* d_index, uint32_t slots,
+                               const uint32_t* d_count, void* d_out, uint64_t out_cap, void* d_gtab,
+                               dmx_inflate_status* d_status, hipStream_t s) {
+    if (zbytes > 0xFFFFFFF0ull) return -(int)E_RANGE;
+    if (!slots) return 0;
+    hipLaunchKernelGGL((dmx_inflate_index_kernel<false, true>), dim3(slots), dim3(64), 0, s, (const uint8_t*)d_z, zbytes,
+                       d_index, (uint8_t*)d_out, out_cap, (uint32_t*)d_gtab, (uint32_t)DMX_BGZF_MAX_ISIZE, d_status, d_count);
+    return hipGetLastError() == hipSuccess ? 0 : -(int)E_DEVICE;
 }
 
 // The members of any BGZF file (include/dmx.h): the indexed decode with the format's own bound on
@@ -1279,7 +1296,7 @@ extern "C" int dmx_inflate_chained_async(const void* d_z, uint64_t zbytes, const
     if (hipMemsetAsync(d_status, 0, sizeof(dmx_inflate_status), s) != hipSuccess) return -(int)E_DEVICE;
     if (hipMemsetAsync(T, 0, 256, s) != hipSuccess) return -(int)E_DEVICE;
     hipLaunchKernelGGL(dmx_inflate_index_kernel<true>, dim3(nblk), dim3(64), 0, s, (const uint8_t*)d_z, zbytes, d_index,
-                       (uint8_t*)cells, out_cap, gtab, (uint32_t)IW, d_status);
+                       (uint8_t*)cells, out_cap, gtab, (uint32_t)IW, d_status, (const uint32_t*)nullptr);
     hipLaunchKernelGGL(dmx_cells_prep_kernel, dim3(nblk), dim3(CHAIN_WG), 0, s, d_index, cells, P, L[0], C[0], T, out_cap, d_status);
     uint32_t rounds = 2;   // pointer jumping: a chain through k blocks takes ~log2(k) + 1 rounds
     while ((1ull << (rounds - 2)) < (uint64_t)nblk && rounds < CHAIN_ROUNDS_MAX) rounds++;

@@ -469,8 +469,83 @@ int dmx_bgzf_index_async(const void* d_z, uint64_t zbytes, uint32_t max_isize, d
  * for the arguments (before any device call), the index's status, or the decode's. */
 int dmx_bgzf_decode_device(const void* d_z, uint64_t zbytes, void* d_out, uint64_t out_cap, uint64_t* out_len,
                            int verify, void* stream);
+/* Batched range reads from a BGZF file in device memory (csrc/dmx_bgzf_ranges.hip, DESIGN.md §3.5
+ * "Reading ranges"): many (offset, length) requests against the decoded bytes of the file become
+ * the set of members they touch, a decode of just those members into scratch, and the requested
+ * bytes packed back to back into d_out -- all on the device, with no host round trip.
+ * d_index / d_crc / nblk are what dmx_bgzf_index_async wrote for d_z: entries in file order, the
+ * first at out_off 0, out_off[m + 1] == out_off[m] + out_len[m], out_len in 1..65536, bit rising; a
+ * thread per entry checks this, a violation is status -E_INVAL and nothing is decoded.  d_crc == NULL:
+ * no verification.  A range is clipped as pread clips: with total = the decoded length of the file,
+ * range q yields min(len, total - off) bytes, or 0 when off >= total; len is any 64-bit value (the
+ * sums saturate, and a saturated sum is above every capacity).  Ranges may overlap, repeat and come
+ * in any order.  The bytes of range q land at d_out + d_out_off[q]; d_out_off (nranges + 1 words,
+ * 8-byte aligned) is the exclusive scan of the clipped lengths, d_out_off[nranges] == out_len, and is
+ * written whenever the status is 0 or -E_SZ.
+ * flags & DMX_RANGES_VIRTUAL: off is a BGZF virtual offset, member file offset << 16 | offset in
+ * the member's data.  off >> 16 must be the file offset of a member that has an index entry: the
+ * member's header is parsed there (bounds-checked, as dmx_bgzf_index_max parses it) and the entry
+ * whose bit is the first bit of its DEFLATE data -- 8 x (offset + 12 + XLEN) for a member without
+ * FNAME / FCOMMENT / FHCRC -- is found by binary search; off & 0xFFFF must be below that member's
+ * out_len unless len == 0.  Any other value makes the call -E_RANGE with bad = the lowest such range
+ * index (an integer minimum: deterministic).  The range then reads on across the following members
+ * like any other.
+ * A member is decoded once, however many ranges touch it, and only if a non-empty clipped range
+ * touches it; untouched members are never read, so a corrupt member or a wrong CRC in one is not an
+ * error of the call.  nmembers > max_members, scratch_len > scratch_bytes or out_len > out_cap is
+ * status -E_SZ: the record then holds all three needed numbers, nothing is decoded and d_out is
+ * untouched.  Status precedence: -E_INVAL (index check), -E_RANGE, -E_SZ, then the decode's first
+ * error (the statuses of dmx_inflate_members_async), then -E_CRC; after any of them d_out is
+ * untouched.
+ * No allocation, no host synchronisation; the number of launches and every grid follow from the
+ * host arguments alone (nblk, nranges, max_members, out_cap) and the device's size, a linear chain
+ * that can be captured into a graph; records and counters are reset by kernels.  Everything the
+ * call needs lives in d_work (256-byte aligned, work_bytes >= dmx_bgzf_ranges_work(nblk, nranges,
+ * max_members, scratch_bytes)): the members' need counts, the scans, the compact sub-index and its
+ * CRC words, the decode's first-level tables and scratch_bytes of decoded members.  With all three
+ * capacities 0 (d_out may be NULL) the call only plans: the record tells what the real call needs.
+ * Returns before any device call: -E_INVAL (d_status, d_work or d_out_off NULL, d_z NULL with
+ * zbytes > 0, d_index NULL with nblk > 0, d_ranges NULL with nranges > 0, d_out NULL with
+ * out_cap > 0; d_index, d_ranges, d_out_off or d_status not 8-byte, d_crc not 4-byte, d_work not
+ * 256-byte aligned; work_bytes too small), -E_RANGE (zbytes > 0xFFFFFFF0, nranges > 0x7FFFFFFF,
+ * unknown flags); else 0 or -E_DEVICE.  nranges == 0 or nblk == 0 is status 0, out_len 0 and
+ * d_out_off[..] = 0. */
+typedef struct { uint64_t off; uint64_t len; } dmx_brange;      /* 16 bytes */
+#define DMX_RANGES_VIRTUAL 1u   /* off is a BGZF virtual offset: member file offset << 16 | offset in the member's data */
+typedef struct {
+    int32_t  status;       /* 0 or -E_* (precedence above) */
+    uint32_t nmembers;     /* distinct members the ranges touch (the capacity needed) */
+    uint64_t out_len;      /* sum of the clipped lengths (bytes of d_out needed) */
+    uint64_t scratch_len;  /* sum of the ISIZEs of the touched members (scratch needed) */
+    uint32_t bad;          /* lowest index of a range that is -E_RANGE, else 0xFFFFFFFF */
+    uint32_t reserved;
+} dmx_bgzf_ranges_status;                                       /* 32 bytes */
+/* Bytes of d_work for an index of nblk entries, nranges ranges, max_members members to decode and
+ * scratch_bytes of decoded members (a multiple of 256, monotone in every argument). */
+uint64_t dmx_bgzf_ranges_work(uint32_t nblk, uint32_t nranges, uint32_t max_members, uint64_t scratch_bytes);
+/* The scans' geometry (tests): members and ranges per scan tile (a workgroup). */
+void dmx_bgzf_ranges_geometry(uint32_t* member_tile, uint32_t* range_tile);
+int dmx_bgzf_read_ranges_async(const void* d_z, uint64_t zbytes,
+                               const dmx_iblock* d_index, const uint32_t* d_crc, uint32_t nblk,
+                               const dmx_brange* d_ranges, uint32_t nranges, uint32_t flags,
+                               void* d_out, uint64_t out_cap, uint64_t* d_out_off,
+                               uint32_t max_members, uint64_t scratch_bytes,
+                               void* d_work, uint64_t work_bytes,
+                               dmx_bgzf_ranges_status* d_status, void* stream);
+/* The convenience over it, with its work buffer from the pool dmx_inflate_async uses: the call above
+ * with all three capacities 0 (plan only), one 32-byte copy of its record to the host -- the call's
+ * one synchronisation before the decode -- then the real call sized by the record, its record and
+ * its status.  *out_len receives the packed length whenever planning succeeded, also when out_cap is
+ * too small (-E_SZ, d_out untouched: the two-call idiom of dmx_bgzf_decode_device); d_out_off is then
+ * written too.  verify != 0 checks the touched members' CRC-32s (d_crc must then be given).  Returns
+ * 0, -E_INVAL / -E_RANGE for the arguments (before any device call), -E_MALLOC, or the record's
+ * status. */
+int dmx_bgzf_read_device(const void* d_z, uint64_t zbytes, const dmx_iblock* d_index, const uint32_t* d_crc,
+                         uint32_t nblk, const dmx_brange* d_ranges, uint32_t nranges, uint32_t flags,
+                         void* d_out, uint64_t out_cap, uint64_t* d_out_off, uint64_t* out_len,
+                         int verify, void* stream);
 /* Host-buffer convenience (H2D, index, decode, D2H) on the cached per-device context
- * dmx_encode_host uses: any BGZF file z[0..zlen) into out.  *out_len receives the decoded length
+ * dmx_encode_host uses: any BGZF file z[0..zlen) into out. *out_len receives the decoded length
  * (the sum of the ISIZEs) whenever the file indexes, also when out_cap is too small (-E_SZ,
  * nothing decoded).  verify != 0 checks every member's CRC-32 on the device (-E_CRC).  An empty
  * file, or one of empty members only, gives 0 bytes and 0.  Returns 0, the index walk's status,
