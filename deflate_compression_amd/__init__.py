@@ -14,6 +14,7 @@ include/dmx.h).  This module is a thin ctypes layer:
     decompress_bgzf(z) -> bytes                           the same from and to host buffers (any BGZF file)
     bgzf_index_gpu(zt) / inflate_bgzf_tensor(zt)          a BGZF file in device memory: indexed and decoded where it lies
     bgzf_read_ranges(zt, ranges) / bgzf_pread(zt, off, n) byte ranges of such a file: only the members they touch are decoded
+    inflate_batch(streams)                                many independent zlib / gzip / raw DEFLATE streams, side by side
     Encoder                                               device-resident encodes
 
 There is no CPU fallback: if libdmx.so is missing the import of this module fails,
@@ -31,6 +32,8 @@ __all__ = [
     "COMPRESS_STATS", "E", "DMX_F_HEADER", "DMX_F_TRAILER", "DMX_F_FINAL", "DMX_ZLIB", "DMX_F_LAZY", "DMX_F_EXACT_SORT", "DMX_F_SPLIT", "DMX_F_DICT", "DMX_F_STORE_CHECK", "DMX_F_DEEP", "DMX_F_GZIP", "DMX_GZIP", "DMX_F_BGZF", "DMX_BGZF", "crc32_combine", "crc32_geometry", "bgzf_index", "inflate_bgzf_gpu", "decompress_bgzf", "bgzf_index_gpu", "inflate_bgzf_tensor", "crc32_ranges", "DMX_BGZF_MAX_ISIZE", "inflate_gpu", "inflate_gpu_chained", "ref_estimates",
     "bgzf_read_ranges", "bgzf_pread", "bgzf_voffset", "bgzf_read_ranges_async", "ranges_geometry", "BRange", "RangesStatus",
     "DMX_RANGES_VIRTUAL",
+    "inflate_batch", "inflate_batch_async", "BStream", "BResult", "BatchStatus", "BRESULT_DTYPE",
+    "DMX_BATCH_AUTO", "DMX_BATCH_ZLIB", "DMX_BATCH_GZIP", "DMX_BATCH_RAW", "DMX_BATCH_MEASURE",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -52,6 +55,8 @@ DMX_F_BGZF = 1024
 DMX_BGZF = DMX_F_BGZF | DMX_F_FINAL
 DMX_BGZF_MAX_ISIZE = 65536
 DMX_RANGES_VIRTUAL = 1
+DMX_BATCH_AUTO, DMX_BATCH_ZLIB, DMX_BATCH_GZIP, DMX_BATCH_RAW = 0, 1, 2, 3
+DMX_BATCH_MEASURE = 16
 _M = 1 << 24
 # src/include/global_errors.h:24-35 and src/include/deflate_errors.h:9-22
 E = {
@@ -102,6 +107,28 @@ class RangesStatus(ctypes.Structure):
     """dmx_bgzf_ranges_status: the 32-byte device record of dmx_bgzf_read_ranges_async"""
     _fields_ = [("status", ctypes.c_int32), ("nmembers", ctypes.c_uint32), ("out_len", ctypes.c_uint64),
                 ("scratch_len", ctypes.c_uint64), ("bad", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class BStream(ctypes.Structure):
+    """dmx_bstream: one stream of dmx_inflate_batch_async -- its input range and its output window"""
+    _fields_ = [("in_off", ctypes.c_uint64), ("in_len", ctypes.c_uint64), ("out_off", ctypes.c_uint64),
+                ("out_cap", ctypes.c_uint64)]
+
+
+class BResult(ctypes.Structure):
+    """dmx_bresult: the 32-byte result of one stream of dmx_inflate_batch_async"""
+    _fields_ = [("status", ctypes.c_int32), ("format", ctypes.c_uint32), ("out_len", ctypes.c_uint64),
+                ("in_used", ctypes.c_uint64), ("check", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class BatchStatus(ctypes.Structure):
+    """dmx_batch_status: the 16-byte summary record of dmx_inflate_batch_async"""
+    _fields_ = [("nfailed", ctypes.c_uint32), ("first_bad", ctypes.c_uint32), ("total_out", ctypes.c_uint64)]
+
+
+# numpy's view of dmx_bresult records
+BRESULT_DTYPE = [("status", "<i4"), ("format", "<u4"), ("out_len", "<u8"), ("in_used", "<u8"), ("check", "<u4"),
+                 ("reserved", "<u4")]
 
 
 class _StringLen(ctypes.Structure):
@@ -158,6 +185,8 @@ def lib() -> ctypes.CDLL:
                                        ctypes.c_int),
         "dmx_bgzf_read_device": ([vp, u64, vp, vp, u32, vp, u32, u32, vp, u64, vp, ctypes.POINTER(u64), ctypes.c_int, vp],
                                  ctypes.c_int),
+        "dmx_inflate_batch_work": ([u32], u64),
+        "dmx_inflate_batch_async": ([vp, u64, vp, u32, u32, vp, u64, vp, vp, u64, vp, vp], ctypes.c_int),
         "dmx_crc32_combine": ([u32, u32, u64], u32),
         "dmx_crc32_geometry": ([u32p, u32p], None),
         "dmx_fd_last_stats": ([ctypes.POINTER(FdStats)], ctypes.c_int),
@@ -612,6 +641,98 @@ def bgzf_pread(zt, off: int, n: int, index=None, verify: bool = True):
             break
     _check(r, "dmx_bgzf_read_device")
     return out
+
+
+_BATCH_FMT = {"auto": DMX_BATCH_AUTO, "zlib": DMX_BATCH_ZLIB, "gzip": DMX_BATCH_GZIP, "raw": DMX_BATCH_RAW}
+
+
+def inflate_batch_async(zt, streams, nstreams: int, flags: int, out, out_bytes: int, results, work, status, stream=None) -> int:
+    """dmx_inflate_batch_async on caller-owned CUDA tensors, enqueued on `stream` (the current one by
+    default) with no synchronisation, so it can be captured into a graph: zt the compressed bytes,
+    streams an (n, 4) int64 tensor of dmx_bstream records (in_off, in_len, out_off, out_cap), flags a
+    DMX_BATCH_* format with or without DMX_BATCH_MEASURE, out the output (None when measuring),
+    results a tensor of 32 x nstreams bytes (BResult records), work a uint8 tensor of
+    lib().dmx_inflate_batch_work(nstreams) bytes (256-byte aligned), status a 16-byte tensor
+    (BatchStatus).  Returns the call's own return code; the outcomes are in the records."""
+    import torch
+    dev = work.device
+    with torch.cuda.device(dev):
+        s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        return lib().dmx_inflate_batch_async(_ptr(zt), zt.numel() if zt is not None else 0, _ptr(streams), nstreams, flags,
+                                             _ptr(out), out_bytes, ctypes.c_void_p(results.data_ptr()),
+                                             ctypes.c_void_p(work.data_ptr()), work.numel(),
+                                             ctypes.c_void_p(status.data_ptr()), ctypes.c_void_p(s))
+
+
+def inflate_batch(z, streams=None, fmt: str = "auto", sizes=None, strict: bool = True):
+    """Inflate many independent zlib streams, gzip members or raw DEFLATE streams on the GPU, side
+    by side (dmx_inflate_batch_async): z is a list of bytes-like objects, packed into one device
+    tensor here, or a contiguous uint8 CUDA tensor with `streams`, an (n, 2) int64 array of
+    (off, len) into it.  fmt: "auto" (1F 8B names a gzip member, anything else a zlib stream),
+    "zlib", "gzip" or "raw".  sizes: the decoded lengths where the caller knows them -- one decode
+    pass, and a length that is too small shows as -E_SZ; without it a measure pass runs first, an
+    exclusive scan of its lengths on the device places the windows, and one synchronisation sizes
+    the output.  Returns (out, offsets, results): the decoded bytes packed back to back as a uint8
+    CUDA tensor, an int64 CUDA tensor of n + 1 with stream k at out[offsets[k]:offsets[k + 1]] (its
+    first results[k].out_len bytes), and a numpy structured array of the BResult records (status,
+    format, out_len, in_used, check).  strict: a stream with a status raises DeflateError with the
+    status of the lowest such index, which the message names."""
+    import numpy as np
+    import torch
+    L = lib()
+    if fmt not in _BATCH_FMT:
+        raise ValueError("fmt is one of " + ", ".join(_BATCH_FMT))
+    flags = _BATCH_FMT[fmt]
+    if isinstance(z, torch.Tensor):
+        if streams is None:
+            raise ValueError("a tensor comes with streams, an (n, 2) int64 array of (off, len)")
+        if z.numel() and (z.dtype != torch.uint8 or not z.is_cuda or not z.is_contiguous()):
+            raise ValueError("inflate_batch takes a contiguous uint8 CUDA tensor")
+        zt = z
+        sa = np.asarray(streams.cpu() if isinstance(streams, torch.Tensor) else streams).astype(np.int64).reshape(-1, 2)
+    else:
+        parts = [bytes(b) for b in z]
+        lens = np.array([len(b) for b in parts], dtype=np.int64)
+        offs = np.concatenate(([0], np.cumsum(lens)[:-1])) if len(parts) else np.zeros(0, np.int64)
+        sa = np.stack([offs, lens], axis=1).astype(np.int64).reshape(-1, 2)
+        zt = torch.frombuffer(bytearray(b"".join(parts) or b"\0"), dtype=torch.uint8).cuda()
+    dev = zt.device
+    n = sa.shape[0]
+    desc = np.zeros((n, 4), dtype=np.int64)
+    desc[:, :2] = sa
+    res = torch.zeros(max(n, 1) * 4, dtype=torch.int64, device=dev)
+    st = torch.empty(2, dtype=torch.int64, device=dev)
+    work = torch.empty(int(L.dmx_inflate_batch_work(n)), dtype=torch.uint8, device=dev)
+    measured = None
+    if sizes is not None:
+        sz = np.asarray(sizes, dtype=np.int64).reshape(-1)
+        if sz.shape[0] != n:
+            raise ValueError("sizes has one length per stream")
+        offsets_h = np.concatenate(([0], np.cumsum(sz))).astype(np.int64)
+        desc[:, 2], desc[:, 3] = offsets_h[:-1], sz
+        dt = torch.from_numpy(desc).to(dev)
+        offsets = torch.from_numpy(offsets_h).to(dev)
+        total = int(offsets_h[-1])
+    else:
+        desc[:, 3] = -1   # UINT64_MAX: no limit
+        dt = torch.from_numpy(desc).to(dev)
+        _check(inflate_batch_async(zt, dt, n, flags | DMX_BATCH_MEASURE, None, 0, res, work, st), "dmx_inflate_batch_async")
+        measured = res.view(max(n, 1), 4)[:n].clone()
+        offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(measured[:, 1], 0, out=offsets[1:])
+        dt[:, 2], dt[:, 3] = offsets[:-1], measured[:, 1]
+        total = int(offsets[-1].item())   # the call's one synchronisation before the decode
+    out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+    _check(inflate_batch_async(zt, dt, n, flags, out, total, res, work, st), "dmx_inflate_batch_async")
+    rt = res.view(max(n, 1), 4)[:n]
+    if measured is not None:
+        # a stream the measure pass refused has a window of 0 bytes: its status is the measured one
+        rt = torch.where((measured[:, 0] & 0xFFFFFFFF != 0)[:, None], measured, rt)
+    results = rt.cpu().numpy().view(np.uint8).reshape(-1).view(BRESULT_DTYPE)
+    rec = BatchStatus.from_buffer_copy(st.cpu().numpy().tobytes())
+    if strict and rec.nfailed:
+        raise DeflateError(int(results["status"][rec.first_bad]), f"inflate_batch: stream {rec.first_bad}")
+    return out[:total], offsets, results
 
 
 def inflate_gpu_chained(z, out_cap: int, index, nblk: int, stream=None, work=None):

@@ -545,6 +545,140 @@ extern "C" int dmx_crc32_ranges_async(const void* d_in, uint64_t n, const dmx_ib
     return dmx_crc32_ranges_launch(d_in, n, d_index, nblk, d_crc, NULL, d_status, (hipStream_t)stream);
 }
 
+// ---- CRC-32 of the gzip members of a batch (dmx_inflate_batch_async: any offset, any length) ----
+//
+//   dmx_crc_batch_kernel   the ranges kernel with an entry's geometry read from the batch's records
+//                          -- out_off of stream k's descriptor, out_len of its result -- and a
+//                          length without a bound: an entry is a loop over pieces of at most CRC_S
+//                          bytes with the ranges kernel's per-piece arithmetic, folded by thread 0
+//                          with the constant x^(8 CRC_S).  The affine term's x^(8 len) is the product
+//                          of the two g_crc_shift entries for len mod 65 536 and, above that, of
+//                          x^(8 65 536 (len >> 16)) by square-and-multiply -- by wave 0 while the
+//                          last piece's loads fly.
+//                          Only an entry with status 0 and format gzip has data; any other is one
+//                          piece without data and is left alone.  The value is compared with the
+//                          stored CRC-32 (check) and the member is finished: -E_CRC, else -E_LEN
+//                          where the decode noted a wrong ISIZE (reserved), else 0; the note is
+//                          cleared, a failed member's out_len / in_used / check become 0, and the
+//                          summary counts the member (integer sums and a minimum).
+__global__ __launch_bounds__(CRC_T) void dmx_crc_batch_kernel(const uint8_t* __restrict__ in, uint64_t n,
+                                                              const dmx_bstream* __restrict__ streams, uint32_t nstreams,
+                                                              dmx_bresult* res, dmx_batch_status* __restrict__ st) {
+    __shared__ __attribute__((aligned(16))) uint32_t tab[CRC_NS * 256];
+    __shared__ __attribute__((aligned(16))) uint32_t stage[CRC_T * CRC_ROW];
+    __shared__ uint32_t wred[CRC_T / 64];
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t i = tid; i < CRC_NS * 256; i += CRC_T) tab[i] = (&g_crc.t[0][0])[i];
+    const uint32_t klane = g_crc.lane[tid];
+    constexpr uint32_t XS = crc_xspan();
+    // piece j of entry k: its aligned base, the data's bytes [lo, hi) from there (hi <= CRC_S), the
+    // entry's pieces and length; false: not a gzip member that decoded (then one piece, no data)
+    auto geom = [&](uint32_t k, uint64_t j, const uint8_t*& base, uint32_t& lo, uint32_t& hi, uint64_t& np, uint64_t& len) {
+        const uint64_t off = streams[k].out_off;
+        len = res[k].out_len;
+        const bool ok = res[k].status == 0 && res[k].format == DMX_BATCH_GZIP && off <= n && len <= n - off;
+        uint64_t elo = 0, ehi = 0;   // the whole entry from its aligned base
+        base = in;
+        if (ok && len) {
+            const uint8_t* p = in + off;
+            elo = reinterpret_cast<uintptr_t>(p) & 15;
+            base = p - elo;
+            ehi = elo + len;
+        }
+        np = ehi > CRC_S ? (ehi + CRC_S - 1) / CRC_S : 1u;
+        base += j * CRC_S;
+        lo = j ? 0u : (uint32_t)elo;
+        const uint64_t left = ehi - j * CRC_S;   // (j < np: ehi > j CRC_S, or both are 0)
+        hi = left < CRC_S ? (uint32_t)left : (uint32_t)CRC_S;
+        return ok;
+    };
+    uint4 v[CRC_Q];
+    auto load = [&](uint32_t k, uint64_t j) {
+        const uint8_t* base;
+        uint32_t lo, hi;
+        uint64_t np, len;
+        geom(k, j, base, lo, hi, np, len);
+#pragma unroll
+        for (uint32_t i = 0; i < CRC_Q; i++) v[i] = crc_load16_blk(base, 16u * (tid + CRC_T * i), lo, hi);
+    };
+    uint32_t k = blockIdx.x, acc = 0;   // acc (thread 0): the raw remainder of the entry's pieces so far
+    uint64_t j = 0;
+    if (k < nstreams) load(k, 0);
+    while (k < nstreams) {
+        const uint8_t* base;
+        uint32_t lo, hi;
+        uint64_t np, len;
+        const bool ok = geom(k, j, base, lo, hi, np, len);
+        const bool last = j + 1 == np;
+        // x^-(8 Z) and the affine term, by wave 0 while the loads fly (thread 0 uses them)
+        uint32_t unshift = 0, affine = 0;
+        if (last && tid < 64) {
+            const uint32_t Z = (CRC_S - hi) & (CRC_S - 1u);   // (no data: R = 0, any factor)
+            const uint64_t l = ok ? len : 0u;
+            unshift = dmx_gf2_mulmod(g_crc_unshift.lo[Z & 255u], g_crc_unshift.hi[Z >> 8]);
+            affine = dmx_gf2_mulmod(g_crc_shift.lo[l & 255u], g_crc_shift.hi[(l >> 8) & 255u]);
+            if (l >> 16) affine = dmx_gf2_mulmod(affine, dmx_gf2_xpow(l >> 16, 19));   // x^(8 65 536 (l >> 16))
+            affine ^= 0xFFFFFFFFu;
+        }
+#pragma unroll
+        for (uint32_t i = 0; i < CRC_Q; i++) {
+            const uint32_t q = tid + CRC_T * i, sl = q / (CRC_L / 16);
+            if (sl * CRC_L < hi)   // (a slice behind the data is never read)
+                *reinterpret_cast<uint4*>(&stage[sl * CRC_ROW + 4 * (q % (CRC_L / 16))]) = v[i];
+        }
+        __syncthreads();   // (and the tables, the first time)
+        const uint32_t kn = last ? k + gridDim.x : k;
+        const uint64_t jn = last ? 0u : j + 1;
+        if (kn < nstreams) load(kn, jn);   // the next piece's loads fly during this one's lookups
+        uint32_t c = 0;
+        if (tid * CRC_L < hi) {
+            const uint4* p = reinterpret_cast<const uint4*>(&stage[tid * CRC_ROW]);
+#pragma unroll
+            for (uint32_t s = 0; s < CRC_L / 16; s++) {
+                const uint4 d = p[s];
+                CRC_STEP16(c, d, tab);
+            }
+        }
+        uint32_t r = dmx_gf2_mulmod(c, klane);
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) r ^= __shfl_xor(r, o);
+        if ((tid & 63) == 0) wred[tid >> 6] = r;
+        __syncthreads();   // (also: every lane has read its slice before the next staging)
+        if (tid == 0) {
+            uint32_t t = 0;
+#pragma unroll
+            for (uint32_t w = 0; w < CRC_T / 64; w++) t ^= wred[w];
+            acc = j ? dmx_gf2_mulmod(acc, XS) ^ t : t;
+            if (last && ok) {
+                const uint32_t val = dmx_gf2_mulmod(acc, unshift) ^ affine;
+                const int32_t fin = val != res[k].check ? -(int32_t)E_CRC : res[k].reserved ? -(int32_t)E_LEN : 0;
+                res[k].reserved = 0;
+                if (fin) {
+                    res[k].status = fin;
+                    res[k].out_len = 0;
+                    res[k].in_used = 0;
+                    res[k].check = 0;
+                    atomicAdd(&st->nfailed, 1u);
+                    atomicMin(&st->first_bad, k);
+                } else {
+                    atomicAdd((unsigned long long*)&st->total_out, (unsigned long long)len);
+                }
+            }
+        }
+        k = kn;
+        j = jn;
+    }
+}
+
+int dmx_crc32_batch_launch(const void* d_out, uint64_t out_bytes, const dmx_bstream* d_streams, uint32_t nstreams,
+                           dmx_bresult* d_results, dmx_batch_status* d_status, hipStream_t s) {
+    if (!nstreams) return 0;
+    const uint32_t gmax = 3 * crc_device_ncu();   // 3 workgroups of 52 KiB LDS per CU
+    hipLaunchKernelGGL(dmx_crc_batch_kernel, dim3(nstreams < gmax ? nstreams : gmax), dim3(CRC_T), 0, s,
+                       (const uint8_t*)d_out, out_bytes, d_streams, nstreams, d_results, d_status);
+    return hipGetLastError() == hipSuccess ? 0 : -(int)E_DEVICE;
+}
+
 extern "C" void dmx_crc32_geometry(uint32_t* span, uint32_t* lane_slice) {
     if (span) *span = CRC_S;
     if (lane_slice) *lane_slice = CRC_L;

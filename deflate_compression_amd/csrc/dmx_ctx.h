@@ -100,6 +100,12 @@ DMX_HIDDEN int hip_fail(hipError_t e, const char* what);
 DMX_HIDDEN int dmx_crc32_ranges_launch(const void* d_in, uint64_t n, const dmx_iblock* d_index, uint32_t nblk,
                                        uint32_t* d_crc, const uint32_t* d_want, dmx_inflate_status* d_status,
                                        hipStream_t s);
+// the CRC-32 pass of dmx_inflate_batch_async (dmx_crc.hip): every stream with status 0 and format
+// gzip is finished -- -E_CRC, else the decode's note of a wrong ISIZE as -E_LEN -- and counted in
+// the summary
+DMX_HIDDEN int dmx_crc32_batch_launch(const void* d_out, uint64_t out_bytes, const dmx_bstream* d_streams,
+                                      uint32_t nstreams, dmx_bresult* d_results, dmx_batch_status* d_status,
+                                      hipStream_t s);
 // `bytes` of device scratch from the inflate's per-device stream-ordered pool (dmx_inflate_dev.hip),
 // allocated on s; NULL when that fails.  The caller frees it with hipFreeAsync on the same stream.
 DMX_HIDDEN void* dmx_itab_scratch(hipStream_t s, uint64_t bytes);

@@ -31,7 +31,8 @@
 #include <string.h>
 
 #include "../../include/dmx.h"
-#include "dmx_ctx.h"   // dmx_crc32_ranges_launch
+#include "dmx_ctx.h"   // dmx_crc32_ranges_launch, dmx_crc32_batch_launch
+#include "dmx_gz_head.h"
 
 #define IW 32768          // window = LDS ring (stream mode; the indexed mode's ring is IWX)
 #ifndef DMX_IWX
@@ -367,6 +368,7 @@ __device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
 }
 
 // Write window bytes [fl, upto) to HBM (upto - fl <= W).  ADLER: fold them into (a, b).
+// STORE = false (the batch decode's measure pass): the same walk without its stores.
 // Cells: window positions [fl, upto) to the cell buffer (2 bytes a position), 8 cells (16
 // bytes) per lane where the destination is 16-byte aligned.
 template <uint32_t W>
@@ -402,7 +404,7 @@ __device__ __forceinline__ void io_flush_cells(InfLDS<W, uint16_t>& S, IOut& o, 
     __syncthreads();
 }
 
-template <bool ADLER, uint32_t W, typename TW>
+template <bool ADLER, bool STORE = true, uint32_t W, typename TW>
 __device__ __forceinline__ void io_flush(InfLDS<W, TW>& S, IOut& o, uint32_t upto, uint32_t lane) {
     if constexpr (sizeof(TW) == 2) {
         io_flush_cells<W>(S, o, upto, lane);
@@ -419,7 +421,7 @@ __device__ __forceinline__ void io_flush(InfLDS<W, TW>& S, IOut& o, uint32_t upt
     const uint32_t head = min(n, (uint32_t)((16 - (((uintptr_t)dst + p) & 15)) & 15));
     if (lane < head) {
         const uint32_t x = S.win[(p + lane) & IM];
-        dst[p + lane] = (uint8_t)x;
+        if constexpr (STORE) dst[p + lane] = (uint8_t)x;
         if (ADLER) { ss += x; tt += (uint64_t)(n - lane) * x; }
     }
     p += head;
@@ -439,7 +441,7 @@ __device__ __forceinline__ void io_flush(InfLDS<W, TW>& S, IOut& o, uint32_t upt
                     w[k] = x;
                 }
             }
-            *(uint4*)&dst[q] = make_uint4(w[0], w[1], w[2], w[3]);
+            if constexpr (STORE) *(uint4*)&dst[q] = make_uint4(w[0], w[1], w[2], w[3]);
             if (ADLER) {
                 const uint32_t rem = upto - q;   // weight of the first byte
                 for (int k = 0; k < 16; k++) {
@@ -451,7 +453,7 @@ __device__ __forceinline__ void io_flush(InfLDS<W, TW>& S, IOut& o, uint32_t upt
         } else if (q < upto) {   // the last partial stride: bytes
             for (uint32_t t = q; t < upto; t++) {
                 const uint32_t x = S.win[t & IM];
-                dst[t] = (uint8_t)x;
+                if constexpr (STORE) dst[t] = (uint8_t)x;
                 if (ADLER) { ss += x; tt += (uint64_t)(upto - t) * x; }
             }
         }
@@ -459,7 +461,7 @@ __device__ __forceinline__ void io_flush(InfLDS<W, TW>& S, IOut& o, uint32_t upt
     if (p < upto && lane == 0) {   // fewer than 16 bytes left after the loop
         for (uint32_t t = p; t < upto; t++) {
             const uint32_t x = S.win[t & IM];
-            dst[t] = (uint8_t)x;
+            if constexpr (STORE) dst[t] = (uint8_t)x;
             if (ADLER) { ss += x; tt += (uint64_t)(upto - t) * x; }
         }
     }
@@ -581,11 +583,16 @@ __device__ __forceinline__ uint32_t isym_run(IBits& r, uint32_t& op, uint32_t& l
 // read their source from the output already flushed to HBM.
 // CELL: the chained decode of dictionary streams -- the window and the output hold 16-bit
 // cells; a match reaching before the sw block's first byte writes reference cells there.
-template <bool RING, bool ADLER, uint32_t W, bool CELL = false>
+// STORE = false: nothing is written to o.out, which may then be NULL -- only with ADLER and
+// W == IW: the asm run then never flushes by itself (fok is 0), the far-source paths below are
+// compiled out, and the run's own far branch needs dist > W, which no distance code spells
+// (24 577 + 8 191 = 32 768).
+template <bool RING, bool ADLER, uint32_t W, bool CELL = false, bool STORE = true>
 __device__ __forceinline__ int iblock(InfLDS<W, typename std::conditional<CELL, uint16_t, uint8_t>::type>& S, IBits& r,
                                       IOut& o, uint32_t* __restrict__ gt, uint32_t lane, bool& last) {
     constexpr uint32_t IM = W - 1, FL = W / 2;
     constexpr uint32_t CS = CELL ? 2 : 1;   // bytes per output position
+    static_assert(STORE || (RING && ADLER && W == IW && !CELL), "without stores: the stream mode's ring only");
     [[maybe_unused]] const unsigned long long ts0 = IST_NOW();
     IST_ADD(o, 6, 1);
     last = ib_bits(r, 1) != 0;
@@ -599,7 +606,7 @@ __device__ __forceinline__ int iblock(InfLDS<W, typename std::conditional<CELL, 
         if (src + len + r.lo > r.hi) return -(int)E_LEN;
         gu8* zs = r.zb + r.lo + src;
         for (uint32_t c0 = 0; c0 < len; c0 += FL) {   // pieces the ring can hold
-            if (RING && o.op - o.fl > W - FL) io_flush<ADLER>(S, o, o.op, lane);
+            if (RING && o.op - o.fl > W - FL) io_flush<ADLER, STORE>(S, o, o.op, lane);
             const uint32_t ce = min(len, c0 + FL);
             for (uint32_t j = c0 + lane; j < ce; j += 64) S.win[(o.op + (j - c0)) & IM] = zs[j];
             o.op += ce - c0;
@@ -717,7 +724,7 @@ __device__ __forceinline__ int iblock(InfLDS<W, typename std::conditional<CELL, 
         }
         if (ex == IX_LIM && RING && op - o.fl >= FL) {
             o.op = op;
-            io_flush<ADLER>(S, o, o.fl + FL, lane);
+            io_flush<ADLER, STORE>(S, o, o.fl + FL, lane);
             op = o.op;
             capr = io_caprel(o);
             continue;
@@ -765,7 +772,7 @@ __device__ __forceinline__ int iblock(InfLDS<W, typename std::conditional<CELL, 
         if (len > capr - op) { err = -(int)E_SZ; break; }
         if (RING && op - o.fl >= FL) {   // half the ring is due before this match
             o.op = op;
-            io_flush<ADLER>(S, o, o.fl + FL, lane);
+            io_flush<ADLER, STORE>(S, o, o.fl + FL, lane);
             op = o.op;
             capr = io_caprel(o);
         }
@@ -927,6 +934,135 @@ __global__ __launch_bounds__(64) void dmx_inflate_stream_kernel(const uint8_t* _
 }
 
 // ------------------------------------------------------------------------------------
+// Batches of independent streams (dmx_inflate_batch_async, include/dmx.h): the stream kernel's
+// body with per-stream parameters.  One wave per workgroup and the IW ring (34 KB of LDS: four
+// workgroups per CU); the grid is what the device holds at once, and a workgroup claims streams
+// from a device counter, in index order, until none is left -- its table area in d_work and its
+// ring serve one stream after the other (a stream's matches never reach before its own first
+// byte: o.ob == 0 and dist > op is -E_HUFDIS, so what the ring held before is never read).
+// Everything per stream is wave-uniform: the descriptor, the framing (dmx_gz_head.h, the text of
+// the host's header checks), the trailers.  The reader hands out zeros past in_len and never
+// loads a byte behind the stream (ib_vload: whole aligned words that end inside it -- the first
+// may begin up to 3 bytes in front, which are shifted out -- and single bytes at its end), so a
+// stream that ends early is -E_LEN through ib_status, not a decode of its neighbour.
+// MEASURE: no store to d_out (iblock / io_flush with STORE = false); out may be NULL, cap is only
+// a limit.  A gzip member's CRC-32 needs the bytes: the decode leaves status 0 and, in reserved, a
+// note of a wrong ISIZE for the CRC pass (dmx_crc_batch_kernel), which finalises the member and
+// counts it in the summary; under MEASURE there is no such pass and a wrong ISIZE is -E_LEN here.
+// ------------------------------------------------------------------------------------
+#define IBATCH_MAX_WG 2048u   // the grid's fixed upper bound: d_work holds this many table areas at most
+
+struct IBatchCtl {   // the first 256 bytes of d_work
+    unsigned long long next;   // the claim counter
+};
+
+__global__ void dmx_inflate_batch_clear_kernel(IBatchCtl* __restrict__ ctl, dmx_batch_status* __restrict__ st) {
+    ctl->next = 0;
+    st->nfailed = 0;
+    st->first_bad = 0xFFFFFFFFu;
+    st->total_out = 0;
+}
+
+template <bool MEASURE>
+__global__ __launch_bounds__(64) void dmx_inflate_batch_kernel(const uint8_t* __restrict__ z, uint64_t zbytes,
+                                                               const dmx_bstream* __restrict__ streams, uint32_t nstreams,
+                                                               uint32_t fmt, uint8_t* out, uint64_t out_bytes,
+                                                               dmx_bresult* __restrict__ res, uint32_t* __restrict__ gtab,
+                                                               IBatchCtl* __restrict__ ctl,
+                                                               dmx_batch_status* __restrict__ st) {
+    __shared__ InfLDS<IW> S;   // the kernel's one __shared__ object: isym_run addresses the ring from LDS 0
+    uint32_t* gt = gtab + (uint64_t)blockIdx.x * ITAB_WORDS;
+    const uint32_t lane = threadIdx.x;
+    for (;;) {
+        unsigned long long claim = 0;
+        if (lane == 0) claim = atomicAdd(&ctl->next, 1ull);
+        const uint64_t k64 = rfl64(claim);
+        if (k64 >= nstreams) break;
+        const uint32_t k = (uint32_t)k64;
+        const uint64_t in_off = rfl64(streams[k].in_off), in_len = rfl64(streams[k].in_len);
+        const uint64_t out_off = rfl64(streams[k].out_off), out_cap = rfl64(streams[k].out_cap);
+        int err = 0;
+        uint32_t format = fmt;   // (0 under AUTO until the first two bytes are read)
+        uint64_t body = 0, olen = 0, used = 0;
+        uint32_t check = 0, note = 0;
+        if (in_off > zbytes || in_len > zbytes - in_off || in_len > 0xFFFFFFF0ull) err = -(int)E_RANGE;
+        if (!MEASURE && (out_off > out_bytes || out_cap > out_bytes - out_off)) err = -(int)E_RANGE;
+        const uint8_t* zs = z + in_off;
+        if (!err) err = dmx_frame_head(zs, in_len, fmt, &format, &body);
+        format = rfl(format);
+        body = rfl64(body);
+        err = (int)rfl((uint32_t)err);
+        IBits r;
+        IOut o;
+#ifdef DMX_INF_STAMPS
+        for (int q = 0; q < INF_NST; q++) o.st[q] = 0;
+#endif
+        o.out = out;
+        o.base = MEASURE ? 0 : out_off;
+        o.ob = 0;
+        o.cap = out_cap;
+        o.op = 0;
+        o.fl = 0;
+        o.a = 1;
+        o.b = 0;
+        if (!err) {
+            ib_init(r, zs, in_len);
+            ib_seek(r, body * 8);
+            // the loop's exit is made uniform for the compiler too (readfirstlane): what the reader
+            // holds in scalar registers is then one value behind the loop, not a value per lane
+            for (;;) {
+                bool last = false;
+                const int e = ib_status(r, iblock<true, true, IW, false, !MEASURE>(S, r, o, gt, lane, last));
+                err = (int)rfl((uint32_t)e);
+                if (err || rfl(last ? 1u : 0u)) break;
+            }
+        }
+        if (!err) {
+            r.wi = rfl(r.wi);
+            r.bc = rfl(r.bc);
+            io_flush<true, !MEASURE>(S, o, o.op, lane);
+            olen = o.ob + o.op;
+            ib_drop(r, r.bc & 7);   // the trailer starts at the next byte; a raw stream ends there
+            // in_used from the reader's position here, in front of the three-way branch, plus the
+            // trailer's size: taken from the reader behind the branch (ib_bytepos), the raw path's
+            // 64-bit word index came out of the compiler undefined (seen in the ISA and
+            // as garbage in_used values; tests/test_gpu_inflate_batch.py checks in_used per format)
+            used = rfl64(ib_used(r) / 8 - r.lo) + (format == DMX_BATCH_ZLIB ? 4u : format == DMX_BATCH_GZIP ? 8u : 0u);
+            if (format == DMX_BATCH_ZLIB) {   // Adler-32, MSB first
+                for (int q = 0; q < 4; q++) check = (check << 8) | ib_bits(r, 8);
+                if (ib_past(r) || ((o.b << 16) | o.a) != check) err = -(int)E_ZADL32;
+            } else if (format == DMX_BATCH_GZIP) {   // CRC-32 and ISIZE, little-endian
+                uint32_t isize = 0;
+                for (int q = 0; q < 4; q++) check |= ib_bits(r, 8) << (8 * q);
+                for (int q = 0; q < 4; q++) isize |= ib_bits(r, 8) << (8 * q);
+                if (ib_past(r)) err = -(int)E_CRC;   // cut inside the trailer
+                else if (isize != (uint32_t)olen) {
+                    if (MEASURE) err = -(int)E_LEN;
+                    else note = 1;   // the CRC is checked first: the CRC pass reports it
+                }
+            }
+        }
+        if (lane == 0) {
+            dmx_bresult v;
+            v.status = err;
+            v.format = format;
+            v.out_len = err ? 0 : olen;
+            v.in_used = err ? 0 : used;
+            v.check = err ? 0 : check;
+            v.reserved = err ? 0 : note;
+            res[k] = v;
+            if (err) {
+                atomicAdd(&st->nfailed, 1u);
+                atomicMin(&st->first_bad, k);
+            } else if (MEASURE || format != DMX_BATCH_GZIP) {   // (a gzip member: the CRC pass counts it)
+                atomicAdd((unsigned long long*)&st->total_out, (unsigned long long)olen);
+            }
+        }
+        __syncthreads();   // the ring and the small arrays are the next stream's
+    }
+}
+
+// ------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------
 
@@ -1035,6 +1171,60 @@ extern "C" int dmx_inflate_members_async(const void* d_z, uint64_t zbytes, const
     const int r = inflate_launch(d_z, zbytes, d_index, nblk, d_out, out_cap, DMX_BGZF_MAX_ISIZE, d_status, s);
     if (r || !d_crc_want) return r;
     return dmx_crc32_ranges_launch(d_out, out_cap, d_index, nblk, NULL, d_crc_want, d_status, s);
+}
+
+// Batches of independent streams.  d_work: [IBatchCtl, 256 B][first-level tables, ITAB_WORDS per
+// workgroup of the largest grid a batch of nstreams can get].
+extern "C" uint64_t dmx_inflate_batch_work(uint32_t nstreams) {
+    return 256 + 4ull * ITAB_WORDS * (nstreams < IBATCH_MAX_WG ? nstreams : IBATCH_MAX_WG);
+}
+
+// workgroups of the batch kernel the current device holds at once (the occupancy API's answer per
+// CU times the CUs, at most IBATCH_MAX_WG), looked up once per device; 0: a device call failed
+static uint32_t ibatch_resident(void) {
+    static uint32_t wg[ITAB_DEVS];
+    int dev = 0, ncu = 0, per = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= ITAB_DEVS) return 0;
+    uint32_t v = __atomic_load_n(&wg[dev], __ATOMIC_RELAXED);
+    if (v) return v;
+    // (both instantiations have the same LDS, the limit; the decode's registers are no fewer)
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, dmx_inflate_batch_kernel<false>, 64, 0) != hipSuccess ||
+        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || per < 1 || ncu < 1)
+        return 0;
+    const uint64_t n = (uint64_t)per * (uint64_t)ncu;
+    v = n < IBATCH_MAX_WG ? (uint32_t)n : IBATCH_MAX_WG;
+    __atomic_store_n(&wg[dev], v, __ATOMIC_RELAXED);
+    return v;
+}
+
+extern "C" int dmx_inflate_batch_async(const void* d_z, uint64_t zbytes, const dmx_bstream* d_streams, uint32_t nstreams,
+                                       uint32_t flags, void* d_out, uint64_t out_bytes, dmx_bresult* d_results,
+                                       void* d_work, uint64_t work_bytes, dmx_batch_status* d_status, void* stream) {
+    const bool measure = (flags & DMX_BATCH_MEASURE) != 0;
+    if (!d_results || !d_status || !d_work || (!d_streams && nstreams) || (!d_z && zbytes) || (!d_out && !measure))
+        return -(int)E_INVAL;
+    if (((uintptr_t)d_streams & 7) || ((uintptr_t)d_results & 7) || ((uintptr_t)d_status & 7)) return -(int)E_INVAL;
+    if (((uintptr_t)d_work & 255) || work_bytes < dmx_inflate_batch_work(nstreams)) return -(int)E_INVAL;
+    const uint32_t fmt = flags & 15u;
+    if ((flags & ~(15u | DMX_BATCH_MEASURE)) || fmt > DMX_BATCH_RAW) return -(int)E_RANGE;
+    hipStream_t s = (hipStream_t)stream;
+    IBatchCtl* ctl = (IBatchCtl*)d_work;
+    uint32_t* gtab = (uint32_t*)((uint8_t*)d_work + 256);
+    hipLaunchKernelGGL(dmx_inflate_batch_clear_kernel, dim3(1), dim3(1), 0, s, ctl, d_status);
+    if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
+    if (!nstreams) return 0;
+    const uint32_t resident = ibatch_resident();
+    if (!resident) return -(int)E_DEVICE;
+    const uint32_t grid = nstreams < resident ? nstreams : resident;
+    if (measure)
+        hipLaunchKernelGGL(dmx_inflate_batch_kernel<true>, dim3(grid), dim3(64), 0, s, (const uint8_t*)d_z, zbytes, d_streams,
+                           nstreams, fmt, (uint8_t*)nullptr, 0ull, d_results, gtab, ctl, d_status);
+    else
+        hipLaunchKernelGGL(dmx_inflate_batch_kernel<false>, dim3(grid), dim3(64), 0, s, (const uint8_t*)d_z, zbytes, d_streams,
+                           nstreams, fmt, (uint8_t*)d_out, out_bytes, d_results, gtab, ctl, d_status);
+    if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
+    if (measure || fmt == DMX_BATCH_ZLIB || fmt == DMX_BATCH_RAW) return 0;   // no gzip member to finish
+    return dmx_crc32_batch_launch(d_out, out_bytes, d_streams, nstreams, d_results, d_status, s);
 }
 
 // ------------------------------------------------------------------------------------

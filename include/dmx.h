@@ -544,6 +544,71 @@ int dmx_bgzf_read_device(const void* d_z, uint64_t zbytes, const dmx_iblock* d_i
                          uint32_t nblk, const dmx_brange* d_ranges, uint32_t nranges, uint32_t flags,
                          void* d_out, uint64_t out_cap, uint64_t* d_out_off, uint64_t* out_len,
                          int verify, void* stream);
+/* Batches of independent streams (csrc/dmx_inflate_dev.hip, DESIGN.md §3.1 "Batches"): nstreams zlib
+ * streams, gzip members or raw DEFLATE streams (RFC 1950 / 1952 / 1951) of any size and unknown
+ * decoded length, decoded side by side, one wave each, every one with a result of its own.
+ * Stream k is d_z[in_off, in_off + in_len) and decodes into d_out[out_off, out_off + out_cap).  Both
+ * offsets may have any alignment.  A stream whose input lies outside d_z[0, zbytes), whose window lies
+ * outside d_out[0, out_bytes), or whose in_len is above 0xFFFFFFF0 (the reader's 32-bit positions)
+ * gets -E_RANGE, and nothing of it is read or written.  Windows that overlap are the caller's error.
+ * The reader loads whole aligned 4-byte words: up to 3 bytes before a stream's first byte, inside the
+ * word that holds it, are read and never looked at (d_z must be readable there, which a stream
+ * inside an allocation always is); the word that holds its last byte is assembled from the stream's
+ * own bytes, and the reader hands out zeros past them.  So a stream that ends early is -E_LEN (or its
+ * trailer's status), never a decode of the bytes behind it; bytes behind a stream's trailer are
+ * ignored, as deflate_decompress ignores them.  The CRC pass loads whole 16-byte aligned groups as
+ * dmx_crc32_async does: up to 15 bytes before and after a decoded range, inside the groups that hold
+ * its first and last byte, are read and never looked at -- d_out must be readable there, which a
+ * window inside an allocation always is.
+ * flags: the framing in bits 0..3 -- DMX_BATCH_AUTO (a stream that begins 1F 8B is gzip, any other
+ * zlib: deflate_decompress's rule), DMX_BATCH_ZLIB, DMX_BATCH_GZIP, DMX_BATCH_RAW -- and
+ * DMX_BATCH_MEASURE.
+ * d_results[k]: status 0 or -E_* for that stream alone (a failing stream never changes a neighbour's
+ * result or bytes); format the framing that was decoded (1, 2 or 3; 0 where -E_RANGE came first
+ * under AUTO); out_len the bytes produced; in_used the input bytes from in_off through the end of the
+ * trailer (zlib: through the Adler-32; gzip: through ISIZE; raw: through the byte that holds the last
+ * bit of the final block), which is what a caller needs to walk concatenated members; check the stored
+ * Adler-32 or CRC-32 (0 for raw).  After an error out_len, in_used and check are 0, and the bytes
+ * inside that stream's own window are unspecified.  No byte outside the windows is ever written.
+ * Statuses: for zlib and gzip what deflate_decompress returns for the same bytes (the table above),
+ * gzip_header's -E_ZHEAD / -E_ZCMPMT / -E_RESERV, -E_CRC for a wrong or cut gzip trailer and -E_LEN for
+ * a wrong ISIZE included (the CRC is checked first, as on the host); an explicit DMX_BATCH_GZIP on
+ * bytes that do not begin 1F 8B is -E_ZHEAD.  A raw stream has the status of the same data behind a
+ * zlib header, minus the trailer's; an empty raw input is -E_LEN.  out_len > out_cap is -E_SZ.
+ * DMX_BATCH_MEASURE: the same decode with every store to d_out left out -- lengths and statuses only.
+ * d_out may be NULL and out_bytes is not looked at; out_cap is only a limit (UINT64_MAX: none) and
+ * out_off is ignored.  Results as above with one difference: a gzip CRC-32 cannot be checked without
+ * the bytes, so a member with a wrong CRC-32 passes (its check field holds the stored value).
+ * Adler-32 and ISIZE are still checked.
+ * d_status: nfailed the number of streams with a status (an integer sum), first_bad the lowest such
+ * index (an integer minimum; 0xFFFFFFFF when none), total_out the sum of out_len over the streams
+ * with status 0 -- nothing depends on the order in which workgroups run.  The record and the claim
+ * counter are reset by a kernel of the call.
+ * Two or three launches (reset, decode; the CRC-32 pass over the gzip members under DMX_BATCH_AUTO
+ * and DMX_BATCH_GZIP unless measuring; the reset alone when nstreams == 0, status 0): no allocation, no host synchronisation, the number of
+ * launches and every grid follow from nstreams, flags and the device's size, a linear chain that can
+ * be captured into a graph.  The decode's grid is the smaller of nstreams, what the device holds at
+ * once (four 34 KB workgroups per CU) and a fixed bound; workgroups claim streams from a counter in
+ * index order.  Everything the call needs lives in d_work (256-byte aligned, work_bytes >=
+ * dmx_inflate_batch_work(nstreams): a multiple of 256, monotone, bounded -- the counter and the
+ * workgroups' first-level tables).
+ * Returns before any device call: -E_INVAL (d_results, d_status or d_work NULL, d_streams NULL with
+ * nstreams > 0, d_z NULL with zbytes > 0, d_out NULL without DMX_BATCH_MEASURE; d_streams, d_results
+ * or d_status not 8-byte aligned; d_work not 256-byte aligned or work_bytes too small), -E_RANGE
+ * (unknown flag bits, a format above 3); else 0 or -E_DEVICE. */
+typedef struct { uint64_t in_off, in_len, out_off, out_cap; } dmx_bstream;      /* 32 bytes */
+typedef struct { int32_t status; uint32_t format; uint64_t out_len; uint64_t in_used;
+                 uint32_t check; uint32_t reserved; } dmx_bresult;               /* 32 bytes */
+typedef struct { uint32_t nfailed; uint32_t first_bad; uint64_t total_out; } dmx_batch_status; /* 16 bytes */
+#define DMX_BATCH_AUTO 0u      /* 1F 8B: gzip, else zlib -- deflate_decompress's rule */
+#define DMX_BATCH_ZLIB 1u
+#define DMX_BATCH_GZIP 2u
+#define DMX_BATCH_RAW  3u      /* RFC 1951 data only, no header, no trailer */
+#define DMX_BATCH_MEASURE 16u  /* decode without writing: lengths and statuses only */
+uint64_t dmx_inflate_batch_work(uint32_t nstreams);
+int dmx_inflate_batch_async(const void* d_z, uint64_t zbytes, const dmx_bstream* d_streams, uint32_t nstreams,
+                            uint32_t flags, void* d_out, uint64_t out_bytes, dmx_bresult* d_results,
+                            void* d_work, uint64_t work_bytes, dmx_batch_status* d_status, void* stream);
 /* Host-buffer convenience (H2D, index, decode, D2H) on the cached per-device context
  * dmx_encode_host uses: any BGZF file z[0..zlen) into out. *out_len receives the decoded length
  * (the sum of the ISIZEs) whenever the file indexes, also when out_cap is too small (-E_SZ,
