@@ -15,6 +15,7 @@ include/dmx.h).  This module is a thin ctypes layer:
     bgzf_index_gpu(zt) / inflate_bgzf_tensor(zt)          a BGZF file in device memory: indexed and decoded where it lies
     bgzf_read_ranges(zt, ranges) / bgzf_pread(zt, off, n) byte ranges of such a file: only the members they touch are decoded
     inflate_batch(streams)                                many independent zlib / gzip / raw DEFLATE streams, side by side
+    compress_batch(bufs)                                  many independent buffers into as many streams, in one chain of launches
     Encoder                                               device-resident encodes
 
 There is no CPU fallback: if libdmx.so is missing the import of this module fails,
@@ -34,6 +35,7 @@ __all__ = [
     "DMX_RANGES_VIRTUAL",
     "inflate_batch", "inflate_batch_async", "BStream", "BResult", "BatchStatus", "BRESULT_DTYPE",
     "DMX_BATCH_AUTO", "DMX_BATCH_ZLIB", "DMX_BATCH_GZIP", "DMX_BATCH_RAW", "DMX_BATCH_MEASURE",
+    "compress_batch", "compress_batch_async", "encode_batch_blocks", "EStream", "EResult", "EBatchStatus", "ERESULT_DTYPE",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -131,6 +133,28 @@ BRESULT_DTYPE = [("status", "<i4"), ("format", "<u4"), ("out_len", "<u8"), ("in_
                  ("reserved", "<u4")]
 
 
+class EStream(ctypes.Structure):
+    """dmx_estream: one buffer of dmx_encode_batch_async -- its input range"""
+    _fields_ = [("in_off", ctypes.c_uint64), ("in_len", ctypes.c_uint64)]
+
+
+class EResult(ctypes.Structure):
+    """dmx_eresult: the 32-byte result of one stream of dmx_encode_batch_async"""
+    _fields_ = [("status", ctypes.c_int32), ("nblocks", ctypes.c_uint32), ("out_off", ctypes.c_uint64),
+                ("out_len", ctypes.c_uint64), ("check", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class EBatchStatus(ctypes.Structure):
+    """dmx_ebatch_status: the 32-byte record of a whole dmx_encode_batch_async call"""
+    _fields_ = [("status", ctypes.c_int32), ("nfailed", ctypes.c_uint32), ("first_bad", ctypes.c_uint32),
+                ("nblocks", ctypes.c_uint32), ("out_len", ctypes.c_uint64), ("in_len", ctypes.c_uint64)]
+
+
+# numpy's view of dmx_eresult records
+ERESULT_DTYPE = [("status", "<i4"), ("nblocks", "<u4"), ("out_off", "<u8"), ("out_len", "<u8"), ("check", "<u4"),
+                 ("reserved", "<u4")]
+
+
 class _StringLen(ctypes.Structure):
     _fields_ = [("str", ctypes.POINTER(ctypes.c_ubyte)), ("len", ctypes.c_size_t)]
 
@@ -187,6 +211,10 @@ def lib() -> ctypes.CDLL:
                                  ctypes.c_int),
         "dmx_inflate_batch_work": ([u32], u64),
         "dmx_inflate_batch_async": ([vp, u64, vp, u32, u32, vp, u64, vp, vp, u64, vp, vp], ctypes.c_int),
+        "dmx_encode_batch_blocks": ([u64, u32, i32], u32),
+        "dmx_encode_batch_bound": ([u64, u32, i32, u32], u64),
+        "dmx_ctx_reserve_batch": ([vp, u32, u32, i32, u32], ctypes.c_int),
+        "dmx_encode_batch_async": ([vp, vp, u64, vp, u32, u32, ctypes.POINTER(Opts), vp, u64, vp, vp, vp], ctypes.c_int),
         "dmx_crc32_combine": ([u32, u32, u64], u32),
         "dmx_crc32_geometry": ([u32p, u32p], None),
         "dmx_fd_last_stats": ([ctypes.POINTER(FdStats)], ctypes.c_int),
@@ -735,6 +763,113 @@ def inflate_batch(z, streams=None, fmt: str = "auto", sizes=None, strict: bool =
     return out[:total], offsets, results
 
 
+_EBATCH_FMT = {"zlib": DMX_ZLIB, "gzip": DMX_GZIP, "raw": DMX_F_FINAL}
+
+
+def encode_batch_blocks(lens, sw: int = 32768) -> int:
+    """The exact block count of a batch whose lengths are known: the sum of max(1, ceil(len / sw))
+    (an empty stream has one empty block, which carries its framing)."""
+    sw = sw or 32768
+    return int(sum(max(1, -(-int(n) // sw)) for n in lens))
+
+
+def compress_batch_async(encoder, t_in, streams, nstreams: int, max_blocks: int, out, out_cap: int, results, status,
+                         opts: Opts | None = None, stream=None) -> int:
+    """dmx_encode_batch_async on caller-owned CUDA tensors, enqueued on `stream` (the current one by
+    default) with no synchronisation, so it can be captured into a graph: t_in the input bytes,
+    streams an (n, 2) int64 tensor of dmx_estream records (in_off, in_len), max_blocks the capacity in
+    blocks (encode_batch_blocks, or lib().dmx_encode_batch_blocks), out the packed output of out_cap
+    bytes, results a tensor of 32 x nstreams bytes (EResult records), status a 32-byte tensor
+    (EBatchStatus).  The encoder must be reserved (Encoder.reserve_batch).  Where the current stream is
+    the legacy default stream (handle 0) the call runs on the encoder's own stream, as
+    Encoder.encode_async does: the caller orders it against the tensors' producers and consumers.
+    Returns the call's own return code; the outcomes are in the records."""
+    import torch
+    dev = out.device
+    o = opts or encoder.opts
+    with torch.cuda.device(dev):
+        s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        return lib().dmx_encode_batch_async(encoder._ctx, _ptr(t_in), t_in.numel() if t_in is not None else 0,
+                                            _ptr(streams), nstreams, max_blocks, ctypes.byref(o),
+                                            ctypes.c_void_p(out.data_ptr()), out_cap,
+                                            ctypes.c_void_p(results.data_ptr()), ctypes.c_void_p(status.data_ptr()),
+                                            ctypes.c_void_p(s))
+
+
+def compress_batch(bufs, streams=None, fmt: str = "zlib", sw: int = 32768, max_chain: int = 0, lazy: bool = False,
+                   flags: int = 0, encoder=None, strict: bool = True):
+    """Compress many independent buffers into as many independent zlib streams, gzip members or raw
+    DEFLATE streams on the GPU, in one chain of launches (dmx_encode_batch_async): bufs is a list of
+    bytes-like objects, packed into one device tensor here, or a contiguous uint8 CUDA tensor with
+    `streams`, an (n, 2) int64 array of (off, len) into it.  fmt: "zlib", "gzip" or "raw"; flags: more
+    parse / block options (DMX_F_DEEP, DMX_F_STORE_CHECK, DMX_F_EXACT_SORT).  Stream k's bytes are what
+    a single encode of buffer k gives with the same options.  Returns (out, offsets, results): the
+    streams packed back to back as a uint8 CUDA tensor, an int64 CUDA tensor of n + 1 with stream k at
+    out[offsets[k]:offsets[k + 1]], and a numpy structured array of the EResult records (status,
+    nblocks, out_off, out_len, check).  One synchronisation.  strict: a stream with a status, or a
+    status of the whole call, raises DeflateError (a stream's names the lowest such index)."""
+    import numpy as np
+    import torch
+    L = lib()
+    if fmt not in _EBATCH_FMT:
+        raise ValueError("fmt is one of " + ", ".join(_EBATCH_FMT))
+    if isinstance(bufs, torch.Tensor):
+        if streams is None:
+            raise ValueError("a tensor comes with streams, an (n, 2) int64 array of (off, len)")
+        if bufs.numel() and (bufs.dtype != torch.uint8 or not bufs.is_cuda or not bufs.is_contiguous()):
+            raise ValueError("compress_batch takes a contiguous uint8 CUDA tensor")
+        tin = bufs
+        sa = np.asarray(streams.cpu() if isinstance(streams, torch.Tensor) else streams).astype(np.int64).reshape(-1, 2)
+    else:
+        parts = [bytes(b) for b in bufs]
+        lens = np.array([len(b) for b in parts], dtype=np.int64)
+        offs = np.concatenate(([0], np.cumsum(lens)[:-1])) if len(parts) else np.zeros(0, np.int64)
+        sa = np.stack([offs, lens], axis=1).astype(np.int64).reshape(-1, 2)
+        dev0 = f"cuda:{encoder.device}" if encoder is not None else "cuda"
+        tin = torch.frombuffer(bytearray(b"".join(parts) or b"\0"), dtype=torch.uint8).to(dev0)
+    dev = tin.device
+    n = sa.shape[0]
+    o = Opts(sw, max_chain, _EBATCH_FMT[fmt] | flags | (DMX_F_LAZY if lazy else 0), 0)
+    # the lengths are known here: the exact block count (a stream outside the tensor has none)
+    total = int(tin.numel())
+    inside = [(0 <= off <= total and 0 <= ln <= total - off) for off, ln in sa.tolist()]
+    good = [int(ln) for (off, ln), ok in zip(sa.tolist(), inside) if ok]
+    nblk = encode_batch_blocks(good, sw)
+    cap = int(L.dmx_encode_batch_bound(sum(good), n, sw, o.flags))
+    own = encoder is None
+    enc = Encoder(dev.index or 0, 0, sw, max_chain, o.flags) if own else encoder
+    # everything runs on one stream: the current one, or a stream of this call's where the current one
+    # is the legacy default stream, whose handle 0 would name the encoder's own (unordered) stream
+    cur = torch.cuda.current_stream(dev)
+    work = cur if cur.cuda_stream else torch.cuda.Stream(dev)
+    work.wait_stream(cur)
+    try:
+        enc.reserve_batch(nblk, n, sw, o.flags)
+        with torch.cuda.stream(work):
+            dt = torch.from_numpy(np.ascontiguousarray(sa)).to(dev) if n else torch.zeros((1, 2), dtype=torch.int64, device=dev)
+            out = torch.empty(cap, dtype=torch.uint8, device=dev)
+            res = torch.zeros(max(n, 1) * 4, dtype=torch.int64, device=dev)
+            st = torch.zeros(4, dtype=torch.int64, device=dev)
+            _check(compress_batch_async(enc, tin, dt, n, nblk, out, cap, res, st, o), "dmx_encode_batch_async")
+            offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)   # out_off of every record, then the total
+            offsets[:n] = res.view(-1, 4)[:n, 1]
+            offsets[n] = st[2]
+            host = torch.cat([st, res]).cpu().numpy()   # the call's one synchronisation
+        for x in (out, offsets):
+            x.record_stream(cur)
+        cur.wait_stream(work)
+    finally:
+        if own:
+            enc.close()
+    rec = EBatchStatus.from_buffer_copy(host[:4].tobytes())
+    results = host[4:4 + 4 * n].view(np.uint8).reshape(-1).view(ERESULT_DTYPE)
+    if strict and rec.status:
+        raise DeflateError(rec.status, "compress_batch")
+    if strict and rec.nfailed:
+        raise DeflateError(int(results["status"][rec.first_bad]), f"compress_batch: stream {rec.first_bad}")
+    return out[:rec.out_len], offsets, results
+
+
 def inflate_gpu_chained(z, out_cap: int, index, nblk: int, stream=None, work=None):
     """Inflate on the GPU a stream whose blocks may reference the block before them
     (DMX_F_DICT streams), all blocks in parallel: each decodes into 16-bit cells with
@@ -855,6 +990,11 @@ class Encoder:
         """Workspace for n bytes of sw-byte blocks, plus the scratch of DMX_F_SPLIT / DMX_F_DICT
         (dmx_ctx_reserve_flags; synchronises only when it allocates)."""
         _check(self._L.dmx_ctx_reserve_flags(self._ctx, n, sw, flags), "dmx_ctx_reserve_flags")
+
+    def reserve_batch(self, max_blocks: int, max_streams: int, sw: int = 32768, flags: int = 0) -> None:
+        """Workspace for batches (compress_batch_async) of up to max_blocks blocks and max_streams
+        streams (dmx_ctx_reserve_batch; synchronises only when it allocates)."""
+        _check(self._L.dmx_ctx_reserve_batch(self._ctx, max_blocks, max_streams, sw, flags), "dmx_ctx_reserve_batch")
 
     def encode_async(self, d_in: int, n: int, d_out: int, cap: int, stream: int | None = None,
                      opts: Opts | None = None) -> None:

@@ -71,6 +71,12 @@ struct dmx_ctx {
     void* split;          // DMX_F_SPLIT: cap_split x SplitScratch (per-block plans of the 10 groups)
     uint64_t cap_split;
     uint32_t want;        // DMX_F_SPLIT / DMX_F_DICT: scratch kept reserved with the workspace
+    // batch encodes (dmx_encode_batch.hip; allocated by dmx_ctx_reserve_batch only)
+    dmx_bblk* btab;       // cap_btab block table entries
+    uint64_t cap_btab;
+    void* bplan;          // the plan's scratch for cap_bstreams streams: head, tile sums, block starts
+    uint64_t cap_bstreams;
+    int last_batch;       // the last encode was a batch (dmx_block_index: -E_INVAL)
     // timing: a ring of event sets so timed encodes never block the host
     int timing;       // bit k: record event k (set_timing: 1 = all six, 0x100 | s = stage s's two)
     hipEvent_t ev[DMX_EV_RING][6];

@@ -39,6 +39,20 @@ typedef struct {
     uint64_t body_bits; /* coded tokens + extra bits + EOB */
 } dmx_subinfo;
 
+/* One entry of a batch encode's block table (dmx_encode_batch_async; 16 B):
+ * where the block's input lies, since blocks of a batch belong to different streams. */
+typedef struct {
+    uint64_t off;       /* input offset of the block's first byte in d_in */
+    uint32_t len;       /* DMX_BB_LEN: its bytes, 0..sw (0: the one block of an empty stream), with
+                         * DMX_BB_FIRST / DMX_BB_LAST for the first / last block of its stream; or
+                         * DMX_BB_VOID: no block (an entry beyond the batch's real block count) */
+    uint32_t stream;    /* index of its stream */
+} dmx_bblk;
+#define DMX_BB_LEN 0xFFFFu
+#define DMX_BB_VOID 0x20000000u
+#define DMX_BB_FIRST 0x40000000u
+#define DMX_BB_LAST 0x80000000u
+
 /* DMX_DEVICES parsed ("0,1,2,3" or "all"): entries written to devs, 0 if unset, -E_INVAL. */
 #ifdef __cplusplus
 extern "C" {

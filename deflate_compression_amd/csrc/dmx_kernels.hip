@@ -2397,19 +2397,31 @@ __device__ __forceinline__ void stored_rest(const uint8_t* __restrict__ d, uint3
 // eight chunks per thread are loaded before pass 0 decides anything, so the block's whole
 // input is in flight during pass 0's test and barriers; otherwise (text: pass 0 rejects the
 // block) they are loaded only for blocks that pass it.
-template <bool SPEC>
+// BATCH (dmx_encode_batch.hip): the block's input and length come from the batch's block table
+// `tab` instead of b * sw; a void entry and an empty stream's block return at once.
+template <bool SPEC, bool BATCH = false>
 __device__ __forceinline__ uint32_t store_check_block(const uint8_t* __restrict__ in, uint64_t n, uint32_t sw,
                                                       dmx_blkinfo* __restrict__ info, uint32_t* __restrict__ tok_g,
                                                       uint32_t* __restrict__ hist_g, uint32_t uni_ok, uint32_t flags,
-                                                      uint32_t* __restrict__ out32, uint64_t out_cap) {
+                                                      uint32_t* __restrict__ out32, uint64_t out_cap,
+                                                      const dmx_bblk* __restrict__ tab = nullptr) {
     __shared__ uint32_t bm[1u << 12];   // the 17-bit presence bitmap (16 KB: 8 workgroups per CU)
     __shared__ uint32_t hist[256];
     __shared__ uint64_t red[10][SCT / 64];
     __shared__ uint32_t pass_s;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t b = blockIdx.x;
-    const uint64_t off = (uint64_t)b * sw;
-    const uint32_t bn = (uint32_t)((n - off) < sw ? (n - off) : sw);
+    uint64_t off;
+    uint32_t bn;
+    if constexpr (BATCH) {
+        const dmx_bblk e = tab[b];
+        if ((e.len & DMX_BB_VOID) || !(e.len & DMX_BB_LEN)) return 0u;
+        off = e.off;
+        bn = e.len & DMX_BB_LEN;
+    } else {
+        off = (uint64_t)b * sw;
+        bn = (uint32_t)((n - off) < sw ? (n - off) : sw);
+    }
     const uint8_t* d = in + off;
     const uint32_t nblk = gridDim.x;
     if (bn < 4096) {
@@ -3059,13 +3071,16 @@ __device__ __forceinline__ uint4 stage16(const uint8_t* __restrict__ d, uint32_t
         if (p + j < bn) w[j >> 2] |= (uint32_t)d[p + j] << (8 * (j & 3));
     return make_uint4(w[0], w[1], w[2], w[3]);
 }
-template <bool DICT, int NBX, bool LOOP = false>
+// BATCH (dmx_encode_batch.hip): the block's input and length come from the batch's block table
+// `tab` instead of b * sw; a void entry and an empty stream's block return at once.
+template <bool DICT, int NBX, bool LOOP = false, bool BATCH = false>
 __device__ __forceinline__ void match_block(const uint32_t b, const uint8_t* __restrict__ in, uint64_t n, uint32_t sw,
                                             int32_t max_chain, uint32_t mflags, uint16_t* __restrict__ dist_g,
                                             const uint16_t* __restrict__ chs, uint32_t* __restrict__ tok_g,
                                             uint32_t* __restrict__ hist_g,
                                             dmx_blkinfo* __restrict__ info, uint64_t* __restrict__ dbg,
-                                            uint32_t* __restrict__ nfallback) {
+                                            uint32_t* __restrict__ nfallback,
+                                            const dmx_bblk* __restrict__ tab = nullptr) {
     __shared__ MatchLDS L;
     __shared__ uint64_t st_search, st_iters, st_w1, st_w23, st_def, tp0[3], st_rounds, st_p3a, st_h4[3], st_lz, st_w1w;
     uint32_t tid = threadIdx.x;
@@ -3074,8 +3089,17 @@ __device__ __forceinline__ void match_block(const uint32_t b, const uint8_t* __r
     // across the whole block
     if (LOOP) asm volatile("" : "+v"(tid));
     const uint32_t lane = tid & 63, wave = wave_of(tid);
-    const uint64_t off = (uint64_t)b * sw;
-    const uint32_t bn = (uint32_t)((n - off) < sw ? (n - off) : sw);
+    uint64_t off;
+    uint32_t bn;
+    if constexpr (BATCH) {
+        const dmx_bblk e = tab[b];
+        if ((e.len & DMX_BB_VOID) || !(e.len & DMX_BB_LEN)) return;
+        off = e.off;
+        bn = e.len & DMX_BB_LEN;
+    } else {
+        off = (uint64_t)b * sw;
+        bn = (uint32_t)((n - off) < sw ? (n - off) : sw);
+    }
     const uint8_t* d = in + off;
     const bool aligned16 = ((reinterpret_cast<uintptr_t>(d) & 15) == 0);
     // a workgroup per block: the block's bytes (the 2 MT chunks below DMX_BLK) are requested
@@ -5070,12 +5094,17 @@ __device__ __forceinline__ void pack_framing(uint32_t* out32, uint32_t flags, ui
     }
 }
 
+// BATCH (dmx_encode_batch.hip): BFINAL and the stored path's input come from the batch's block
+// table entry `tab[b]`; K2 ran without DMX_F_FINAL, so a coded block's BFINAL is ORed in here, and
+// the streams' headers and trailers are the batch's finish kernel's, not pack_framing's.
+template <bool BATCH = false>
 __device__ __forceinline__ void pack_one(const uint32_t b, const uint8_t* __restrict__ in, uint32_t sw,
                                          const uint32_t* __restrict__ tok_g, const uint32_t* __restrict__ codes_g,
                                          const uint32_t* __restrict__ hdr_g, const dmx_blkinfo* __restrict__ info,
                                          const dmx_subinfo* __restrict__ sub_g,
                                          uint32_t nblk, uint32_t flags, uint32_t* __restrict__ out32,
-                                         dmx_result* __restrict__ res, const uint32_t* __restrict__ bcrc) {
+                                         dmx_result* __restrict__ res, const uint32_t* __restrict__ bcrc,
+                                         const dmx_bblk* __restrict__ tab = nullptr) {
     __shared__ uint32_t stage[PK_RING];
     __shared__ uint32_t code[DMX_HIST];
     // one entry per first piece of a token, value | bits << 24: literals 0..255, then the
@@ -5089,7 +5118,9 @@ __device__ __forceinline__ void pack_one(const uint32_t b, const uint8_t* __rest
     const uint64_t O = bi.off_bits, Lb = bi.len_bits;
     const uint32_t s0 = (uint32_t)(O & 31);
     const uint32_t nwords = (uint32_t)((s0 + Lb + 31) >> 5);
-    const uint32_t final_bit = block_is_final(flags, b, nblk);
+    uint32_t final_bit;
+    if constexpr (BATCH) final_bit = (tab[b].len & DMX_BB_LAST) ? 1u : 0u;
+    else final_bit = block_is_final(flags, b, nblk);
     // DMX_F_BGZF: the member's header and trailer around the data (bcrc: the blocks' CRC-32s).  The
     // data's first and last words are then shared with those, not with a neighbour: same atomicOr.
     if (tid == 0 && (flags & DMX_F_BGZF)) bgzf_member_framing(out32, O, Lb, bcrc[b], bi.n);
@@ -5100,7 +5131,9 @@ __device__ __forceinline__ void pack_one(const uint32_t b, const uint8_t* __rest
         // the block and byte alignment in registers; the first word, the ragged ends and
         // unaligned blocks take the bytewise path.  The first and last words are shared
         // with the neighbouring blocks (zeroed by the scan kernel): atomicOr there.
-        const uint8_t* d = in + (uint64_t)b * sw;
+        const uint8_t* d;
+        if constexpr (BATCH) d = in + tab[b].off;
+        else d = in + (uint64_t)b * sw;
         const uint32_t bn = bi.n;
         const uint32_t P = (s0 + 3 + 7) & ~7u, B0 = (P + 32) >> 3;
         const uint32_t lenw = (bn & 0xFFFFu) | ((~bn & 0xFFFFu) << 16);
@@ -5124,7 +5157,7 @@ __device__ __forceinline__ void pack_one(const uint32_t b, const uint8_t* __rest
         };
         const bool dal = (reinterpret_cast<uintptr_t>(d) & 3) == 0;
         // K0's speculative copy landed where the scan put the block: its quads are written
-        const bool spec = bi.prestored == 3 && O == spec_stored_bit(b, sw, flags);
+        const bool spec = !BATCH && bi.prestored == 3 && O == spec_stored_bit(b, sw, flags);
         const uint32_t ks = 4 - (uint32_t)(gw0 & 3);                      // first quad: (gw0 + ks) % 4 == 0, ks >= 1
         const uint32_t nq = (dal && nwords > ks + 1) ? (nwords - 1 - ks) >> 2 : 0;   // quads short of the last word
         // With the copy in place only the first two and the last two quads can need words of
@@ -5159,7 +5192,8 @@ __device__ __forceinline__ void pack_one(const uint32_t b, const uint8_t* __rest
             const uint32_t k = nq ? (r < ks ? r : kq + (r - ks)) : r;
             put_word(k, gen_word(k));
         }
-        if (tid == 0 && (b == 0 || b == nblk - 1)) pack_framing(out32, flags, nblk, b, res);
+        if constexpr (!BATCH)
+            if (tid == 0 && (b == 0 || b == nblk - 1)) pack_framing(out32, flags, nblk, b, res);
         return;
     }
     // coded blocks: the bits go through an 8 KB LDS ring (PK_RING words) that is flushed to
@@ -5235,6 +5269,8 @@ __device__ __forceinline__ void pack_one(const uint32_t b, const uint8_t* __rest
                 const uint32_t nb = (hb - 32 * k) < 32 ? (hb - 32 * k) : 32;
                 st_or64(stage, pos - 32 * base + 32 * k, hg[k], nb);
             }
+            if constexpr (BATCH)   // BFINAL: the first bit of the block's first header
+                if (sb == 0 && tid == 0 && final_bit) st_or64(stage, pos - 32 * base, 1u, 1);
             pos += hb;
             // tokens: TPT consecutive tokens per thread; a per-thread bit accumulator flushes
             // whole words into the zeroed ring, every one by atomicOr (the first and last are
@@ -5313,7 +5349,8 @@ __device__ __forceinline__ void pack_one(const uint32_t b, const uint8_t* __rest
     }
     __syncthreads();
     for (uint32_t k = tid; base + k < nwords; k += PT) out_word(base + k, stage[k]);
-    if (tid == 0 && (b == 0 || b == nblk - 1)) pack_framing(out32, flags, nblk, b, res);
+    if constexpr (!BATCH)
+        if (tid == 0 && (b == 0 || b == nblk - 1)) pack_framing(out32, flags, nblk, b, res);
 }
 
 // K4: one workgroup per block (wl == nullptr), or a grid that strides over the apply
@@ -5596,6 +5633,8 @@ extern "C" void dmx_ctx_destroy(dmx_ctx* c) {
     if (c->chs) (void)hipFree(c->chs);
     if (c->che) (void)hipFree(c->che);
     if (c->split) (void)hipFree(c->split);
+    if (c->btab) (void)hipFree(c->btab);
+    if (c->bplan) (void)hipFree(c->bplan);
     for (int j = 0; j < DMX_EV_RING; j++)
         for (int k = 0; k < 6; k++) if (c->ev[j][k]) (void)hipEventDestroy(c->ev[j][k]);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -5837,6 +5876,7 @@ extern "C" int dmx_encode_async(dmx_ctx* c, const void* d_in, uint64_t n, void* 
     HIPCHK(fault_hit(2) ? hipErrorLaunchFailure : hipGetLastError());
     c->last_nblk = nblk;
     c->last_sw = (uint32_t)o.sw;
+    c->last_batch = 0;
     return 0;
 }
 
@@ -5893,6 +5933,7 @@ __global__ void dmx_index_kernel(const dmx_blkinfo* __restrict__ info, uint32_t 
 
 extern "C" int dmx_block_index(dmx_ctx* c, dmx_iblock* d_index, uint32_t cap, void* stream) {
     if (!c || !d_index) return -(int)E_INVAL;
+    if (c->last_batch) return -(int)E_INVAL;   // a batch's blocks are not at b * sw (dmx_encode_batch_async)
     if (cap < c->last_nblk) return -(int)E_RANGE;
     if (!c->last_nblk) return 0;
     HIPCHK(hipSetDevice(c->device));
@@ -5964,3 +6005,7 @@ extern "C" int dmx_last_subblock(dmx_ctx* c, uint32_t blk, uint32_t sub, uint32_
     return (int)bi.nsub;
 }
 
+// Batches of independent buffers into independent streams (dmx_encode_batch_async): the plan, the
+// batch instantiations of K0 / K1 / K4, K3's batch layout and the per-stream finish have a file of
+// their own, compiled into this translation unit as dmx_crc.hip is.
+#include "dmx_encode_batch.hip"

@@ -609,6 +609,73 @@ uint64_t dmx_inflate_batch_work(uint32_t nstreams);
 int dmx_inflate_batch_async(const void* d_z, uint64_t zbytes, const dmx_bstream* d_streams, uint32_t nstreams,
                             uint32_t flags, void* d_out, uint64_t out_bytes, dmx_bresult* d_results,
                             void* d_work, uint64_t work_bytes, dmx_batch_status* d_status, void* stream);
+/* Batches of independent buffers into independent streams (csrc/dmx_encode_batch.hip):
+ * the encode's counterpart of dmx_inflate_batch_async.  nstreams buffers become nstreams complete
+ * zlib streams, gzip members or raw DEFLATE streams, every one decodable on its own, in one chain of
+ * launches: blocks are independent, so a thousand 100 KB buffers are the same workgroups as one
+ * 100 MB buffer.
+ * Stream k is d_in[in_off, in_off + in_len): any alignment, gaps and overlaps between streams
+ * allowed.  Its output is written at d_out + d_results[k].out_off; the streams are packed back to
+ * back in index order, each from a byte boundary: d_results[k + 1].out_off == d_results[k].out_off +
+ * d_results[k].out_len, and d_status->out_len is the total.  The bytes of stream k are exactly what
+ * dmx_encode_async writes for that buffer alone with the same opts (an empty buffer: the empty
+ * input's stream, zlib 78 9C 03 00 00 00 00 01, raw 03 00, gzip 20 bytes); check is the stream's
+ * Adler-32, its CRC-32 under DMX_F_GZIP, 0 for a raw stream.  The CRC pass loads whole 16-byte aligned
+ * groups as dmx_crc32_async does: up to 15 bytes before and after a buffer, inside the groups that
+ * hold its first and last byte, are read and never looked at -- d_in must be readable there, which
+ * a buffer inside an allocation always is.
+ * opts->flags must frame a complete stream: DMX_ZLIB, DMX_GZIP, or DMX_F_FINAL alone (raw RFC 1951).
+ * Without DMX_F_FINAL, with only one of DMX_F_HEADER / DMX_F_TRAILER, with DMX_F_GZIP but no
+ * header, or with DMX_F_DICT, DMX_F_SPLIT or DMX_F_BGZF the call returns -E_INVAL.  The parse and
+ * block options work as in a single encode: max_chain (0 = exhaustive), DMX_F_LAZY, DMX_F_DEEP with
+ * deep_chain, DMX_F_STORE_CHECK, DMX_F_EXACT_SORT, any sw.
+ * The descriptors are device memory, so the grids follow from max_blocks, the caller's capacity:
+ * dmx_encode_batch_blocks gives a safe one, and a caller who knows the lengths passes the exact sum
+ * of max(1, ceil(in_len / sw)) over the streams (an empty stream has one empty block, which carries
+ * its framing).  Workgroups beyond the real block count return at once.  No allocation, no host
+ * synchronisation, a linear chain of launches whose number and grids follow from nstreams,
+ * max_blocks, opts and the device's size, capturable into a graph; every record and counter is
+ * reset by a kernel of the call.
+ * Per stream: one that lies outside d_in[0, in_bytes) (a test that cannot wrap) gets -E_RANGE,
+ * out_len 0 and nblocks 0 (its out_off is where the next stream begins); its neighbours keep the
+ * bytes they would have had.  d_status->nfailed is an integer sum and first_bad an integer minimum
+ * (0xFFFFFFFF when none): nothing depends on the order in which workgroups run.
+ * The whole call: d_status->status = -E_SZ when the batch needs more than max_blocks blocks (the
+ * record then holds the needed nblocks; nothing was encoded, so out_len and every stream's out_off
+ * and out_len are 0), or when (out_len + 3) & ~3 exceeds out_cap, dmx_encode_async's own rule (the
+ * record then holds the needed out_len, and d_results[*].out_off / out_len are written).  After
+ * -E_SZ no byte of d_out is written: the two-call idiom of dmx_bgzf_read_ranges_async.  On success no
+ * byte at or beyond (out_len + 3) & ~3 is written.  d_status->in_len is the sum of in_len over the
+ * streams with status 0.
+ * dmx_encode_result after a batch gives the totals: n, ntokens, the block counts (an empty stream's
+ * block counts as a fixed one), out_len, status, and adler 0.  dmx_block_index after a batch is
+ * -E_INVAL: its out_off = b * sw has no meaning there.
+ * The context must be reserved with dmx_ctx_reserve_batch(ctx, max_blocks, max_streams, sw, flags),
+ * the only place that allocates (synchronising when it does): the workspace for max_blocks blocks,
+ * the block table, and the plan's scratch for max_streams streams.  A batch runs without the work
+ * lists, the uniform-block dedupe and the noise check's speculative copy, and it leaves no
+ * launch-shape hint: single encodes on the same context before and after it are unaffected.
+ * dmx_encode_batch_blocks: a bound on the blocks of any nstreams buffers of total_in bytes together,
+ * total_in / sw + nstreams.  dmx_encode_batch_bound: a bound on d_status->out_len rounded up to 4 for
+ * them, at least the sum of dmx_max_compressed_flags(in_len_k, sw, flags) rounded up to 4.  Both are
+ * monotone in total_in and nstreams (sw 0 = 32768; values that do not fit saturate).
+ * Returns before any device call: -E_INVAL (ctx, d_results, d_status or d_out NULL, d_in NULL with
+ * in_bytes > 0, d_streams NULL with nstreams > 0; d_streams, d_results or d_status not 8-byte
+ * aligned, d_out not 4-byte aligned; the flags above), -E_RANGE (sw, max_chain, deep_chain, as
+ * dmx_encode_async checks them; nstreams or max_blocks above 0x7FFFFFFF), -E_SZ (the context is not
+ * reserved for max_blocks blocks or nstreams streams); else 0 or -E_DEVICE. */
+typedef struct { uint64_t in_off, in_len; } dmx_estream;                 /* 16 bytes */
+typedef struct { int32_t status; uint32_t nblocks; uint64_t out_off; uint64_t out_len;
+                 uint32_t check; uint32_t reserved; } dmx_eresult;       /* 32 bytes */
+typedef struct { int32_t status; uint32_t nfailed; uint32_t first_bad; uint32_t nblocks;
+                 uint64_t out_len; uint64_t in_len; } dmx_ebatch_status; /* 32 bytes */
+uint32_t dmx_encode_batch_blocks(uint64_t total_in, uint32_t nstreams, int32_t sw);
+uint64_t dmx_encode_batch_bound(uint64_t total_in, uint32_t nstreams, int32_t sw, uint32_t flags);
+int dmx_ctx_reserve_batch(dmx_ctx* ctx, uint32_t max_blocks, uint32_t max_streams, int32_t sw, uint32_t flags);
+int dmx_encode_batch_async(dmx_ctx* ctx, const void* d_in, uint64_t in_bytes,
+                           const dmx_estream* d_streams, uint32_t nstreams, uint32_t max_blocks,
+                           const dmx_opts* opts, void* d_out, uint64_t out_cap,
+                           dmx_eresult* d_results, dmx_ebatch_status* d_status, void* stream);
 /* Host-buffer convenience (H2D, index, decode, D2H) on the cached per-device context
  * dmx_encode_host uses: any BGZF file z[0..zlen) into out. *out_len receives the decoded length
  * (the sum of the ISIZEs) whenever the file indexes, also when out_cap is too small (-E_SZ,
