@@ -15,6 +15,7 @@ include/dmx.h).  This module is a thin ctypes layer:
     bgzf_index_gpu(zt) / inflate_bgzf_tensor(zt)          a BGZF file in device memory: indexed and decoded where it lies
     bgzf_read_ranges(zt, ranges) / bgzf_pread(zt, off, n) byte ranges of such a file: only the members they touch are decoded
     inflate_batch(streams)                                many independent zlib / gzip / raw DEFLATE streams, side by side
+                                                          (zdict=: preset dictionaries, zlib's FDICT / inflateSetDictionary)
     compress_batch(bufs)                                  many independent buffers into as many streams, in one chain of launches
     Encoder                                               device-resident encodes
 
@@ -30,11 +31,12 @@ import struct
 __all__ = [
     "DeflateError", "Opts", "Result", "Encoder", "lib", "compress", "deflate_compress",
     "deflate_decompress", "max_compressed", "adler32_combine", "gen_text", "gen_random",
-    "COMPRESS_STATS", "E", "DMX_F_HEADER", "DMX_F_TRAILER", "DMX_F_FINAL", "DMX_ZLIB", "DMX_F_LAZY", "DMX_F_EXACT_SORT", "DMX_F_SPLIT", "DMX_F_DICT", "DMX_F_STORE_CHECK", "DMX_F_DEEP", "DMX_F_GZIP", "DMX_GZIP", "DMX_F_BGZF", "DMX_BGZF", "crc32_combine", "crc32_geometry", "bgzf_index", "inflate_bgzf_gpu", "decompress_bgzf", "bgzf_index_gpu", "inflate_bgzf_tensor", "crc32_ranges", "DMX_BGZF_MAX_ISIZE", "inflate_gpu", "inflate_gpu_chained", "ref_estimates",
+    "COMPRESS_STATS", "E", "DMX_F_HEADER", "DMX_F_TRAILER", "DMX_F_FINAL", "DMX_ZLIB", "DMX_F_LAZY", "DMX_F_EXACT_SORT", "DMX_F_SPLIT", "DMX_F_DICT", "DMX_F_STORE_CHECK", "DMX_F_DEEP", "DMX_F_GZIP", "DMX_GZIP", "DMX_F_BGZF", "DMX_BGZF", "DMX_F_FDICT", "crc32_combine", "crc32_geometry", "bgzf_index", "inflate_bgzf_gpu", "decompress_bgzf", "bgzf_index_gpu", "inflate_bgzf_tensor", "crc32_ranges", "DMX_BGZF_MAX_ISIZE", "inflate_gpu", "inflate_gpu_chained", "ref_estimates",
     "bgzf_read_ranges", "bgzf_pread", "bgzf_voffset", "bgzf_read_ranges_async", "ranges_geometry", "BRange", "RangesStatus",
     "DMX_RANGES_VIRTUAL",
     "inflate_batch", "inflate_batch_async", "BStream", "BResult", "BatchStatus", "BRESULT_DTYPE",
     "DMX_BATCH_AUTO", "DMX_BATCH_ZLIB", "DMX_BATCH_GZIP", "DMX_BATCH_RAW", "DMX_BATCH_MEASURE",
+    "inflate_batch_dict_async", "inflate_dict_host", "BDict", "DMX_BATCH_NODICT",
     "compress_batch", "compress_batch_async", "encode_batch_blocks", "EStream", "EResult", "EBatchStatus", "ERESULT_DTYPE",
 ]
 
@@ -55,10 +57,12 @@ DMX_F_GZIP = 512
 DMX_GZIP = DMX_ZLIB | DMX_F_GZIP
 DMX_F_BGZF = 1024
 DMX_BGZF = DMX_F_BGZF | DMX_F_FINAL
+DMX_F_FDICT = 2048
 DMX_BGZF_MAX_ISIZE = 65536
 DMX_RANGES_VIRTUAL = 1
 DMX_BATCH_AUTO, DMX_BATCH_ZLIB, DMX_BATCH_GZIP, DMX_BATCH_RAW = 0, 1, 2, 3
 DMX_BATCH_MEASURE = 16
+DMX_BATCH_NODICT = 0xFFFFFFFF
 _M = 1 << 24
 # src/include/global_errors.h:24-35 and src/include/deflate_errors.h:9-22
 E = {
@@ -126,6 +130,11 @@ class BResult(ctypes.Structure):
 class BatchStatus(ctypes.Structure):
     """dmx_batch_status: the 16-byte summary record of dmx_inflate_batch_async"""
     _fields_ = [("nfailed", ctypes.c_uint32), ("first_bad", ctypes.c_uint32), ("total_out", ctypes.c_uint64)]
+
+
+class BDict(ctypes.Structure):
+    """dmx_bdict: one preset dictionary of dmx_inflate_batch_dict_async -- its range in the dictionary buffer"""
+    _fields_ = [("off", ctypes.c_uint64), ("len", ctypes.c_uint64)]
 
 
 # numpy's view of dmx_bresult records
@@ -211,6 +220,11 @@ def lib() -> ctypes.CDLL:
                                  ctypes.c_int),
         "dmx_inflate_batch_work": ([u32], u64),
         "dmx_inflate_batch_async": ([vp, u64, vp, u32, u32, vp, u64, vp, vp, u64, vp, vp], ctypes.c_int),
+        "dmx_inflate_batch_dict_work": ([u32, u32], u64),
+        "dmx_inflate_batch_dict_async": ([vp, u64, vp, u32, u32, vp, u64, vp, u32, vp, vp, u64, vp, vp, u64, vp, vp],
+                                         ctypes.c_int),
+        "dmx_inflate_dict_host": ([vp, u64, u32, vp, u64, ctypes.POINTER(vp), ctypes.POINTER(u64), ctypes.POINTER(u64)],
+                                  ctypes.c_int),
         "dmx_encode_batch_blocks": ([u64, u32, i32], u32),
         "dmx_encode_batch_bound": ([u64, u32, i32, u32], u64),
         "dmx_ctx_reserve_batch": ([vp, u32, u32, i32, u32], ctypes.c_int),
@@ -280,27 +294,33 @@ def fd_last_stats() -> dict | None:
 
 
 def max_compressed(n: int, sw: int = 32768, flags: int = DMX_ZLIB) -> int:
-    """Worst-case stream bytes for n input bytes (12 more for the gzip container, DMX_F_GZIP;
+    """Worst-case stream bytes for n input bytes (12 more for the gzip container, DMX_F_GZIP; 4 more
+    for a DICTID, DMX_F_FDICT;
     26 more per block and 28 for the end-of-file member under DMX_F_BGZF)."""
     return int(lib().dmx_max_compressed_flags(n, sw, flags))
 
 
 def compress(data, sw: int = 32768, max_chain: int = 0, flags: int = DMX_ZLIB, lazy: bool = False,
              split: bool = False, dict: bool = False, pre=None, store_check: bool = False,
-             deep: bool = False, gzip: bool = False, bgzf: bool = False) -> bytes:
+             deep: bool = False, gzip: bool = False, bgzf: bool = False, fdict: bool = False) -> bytes:
     """Encode a host buffer on the GPU; returns the zlib stream (or raw DEFLATE with flags;
     gzip = a gzip member around the same DEFLATE data, DMX_F_GZIP; bgzf = a gzip member per
     sw block and the end-of-file member, DMX_BGZF -- not with split or dict).
     lazy = f2 lazy parse (DMX_F_LAZY), split = f3 adaptive block splitting (DMX_F_SPLIT),
     dict = f1 cross-block dictionary (DMX_F_DICT; pre = the bytes before `data`),
     store_check = noise blocks stored without a parse (DMX_F_STORE_CHECK),
-    deep = adaptive chain depth of small-alphabet blocks (DMX_F_DEEP)."""
+    deep = adaptive chain depth of small-alphabet blocks (DMX_F_DEEP),
+    fdict = with dict and pre: the zlib header names `pre` as the stream's preset dictionary (78 BB
+    and the DICTID, DMX_F_FDICT), so zlib.decompressobj(zdict=pre) and inflate_batch(zdict=pre)
+    decode it; 1 <= len(pre) <= sw."""
     L = lib()
     p, n, keep = _buf(data)
     if gzip:
         flags |= DMX_F_GZIP
     if bgzf:
         flags |= DMX_BGZF
+    if fdict:
+        flags |= DMX_F_FDICT
     cap = max_compressed(n, sw, flags)
     out = ctypes.create_string_buffer(cap)
     olen = ctypes.c_uint64(0)
@@ -692,7 +712,77 @@ def inflate_batch_async(zt, streams, nstreams: int, flags: int, out, out_bytes: 
                                              ctypes.c_void_p(status.data_ptr()), ctypes.c_void_p(s))
 
 
-def inflate_batch(z, streams=None, fmt: str = "auto", sizes=None, strict: bool = True):
+def inflate_batch_dict_async(zt, streams, nstreams: int, flags: int, dict_t, dicts, ndicts: int, dict_of, out,
+                             out_bytes: int, results, work, status, stream=None) -> int:
+    """dmx_inflate_batch_dict_async on caller-owned CUDA tensors, as inflate_batch_async (no
+    synchronisation: it can be captured into a graph): dict_t the dictionaries' bytes (uint8), dicts an
+    (ndicts, 2) int64 tensor of dmx_bdict records (off, len) into it, dict_of an int32 / uint32 tensor
+    with a dictionary index per stream (DMX_BATCH_NODICT, or -1 as int32: none) or None (every stream
+    uses dictionary 0), work of lib().dmx_inflate_batch_dict_work(nstreams, ndicts) bytes."""
+    import torch
+    dev = work.device
+    with torch.cuda.device(dev):
+        s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        return lib().dmx_inflate_batch_dict_async(_ptr(zt), zt.numel() if zt is not None else 0, _ptr(streams), nstreams, flags,
+                                                  _ptr(dict_t), dict_t.numel() if dict_t is not None else 0, _ptr(dicts),
+                                                  ndicts, _ptr(dict_of), _ptr(out), out_bytes,
+                                                  ctypes.c_void_p(results.data_ptr()), ctypes.c_void_p(work.data_ptr()),
+                                                  work.numel(), ctypes.c_void_p(status.data_ptr()), ctypes.c_void_p(s))
+
+
+def inflate_dict_host(z, zdict=None, fmt: str = "auto"):
+    """One stream on the host with a preset dictionary (dmx_inflate_dict_host): what
+    zlib.decompressobj(wbits, zdict=zdict) makes of z -- a zlib stream with FDICT whose DICTID names
+    zdict, a zlib stream without FDICT (zdict is ignored), a raw stream (fmt="raw": zdict always
+    primes the window) or a gzip member.  zdict=None: no dictionary.  Returns (bytes, in_used);
+    raises DeflateError with the stream's status."""
+    if fmt not in _BATCH_FMT:
+        raise ValueError("fmt is one of " + ", ".join(_BATCH_FMT))
+    zp, zn, zk = _buf(z)
+    dp, dn, dk = _buf(zdict) if zdict is not None else (ctypes.c_void_p(0), 0, None)
+    out, olen, used = ctypes.c_void_p(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    r = lib().dmx_inflate_dict_host(zp, zn, _BATCH_FMT[fmt], dp, dn, ctypes.byref(out), ctypes.byref(olen), ctypes.byref(used))
+    del zk, dk
+    if r != 0:
+        raise DeflateError(r, "dmx_inflate_dict_host")
+    res = ctypes.string_at(out, olen.value)
+    _libc.free(out)
+    return res, int(used.value)
+
+
+def _batch_dicts(zdict, dicts, dict_of, n: int, dev):
+    """(dict_t, dicts_t, ndicts, dict_of_t) on dev from inflate_batch's zdict / dicts / dict_of"""
+    import numpy as np
+    import torch
+    if isinstance(zdict, torch.Tensor):
+        if dicts is None:
+            raise ValueError("a dictionary tensor comes with dicts, an (n, 2) int64 array of (off, len)")
+        if zdict.numel() and (zdict.dtype != torch.uint8 or not zdict.is_cuda or not zdict.is_contiguous()):
+            raise ValueError("zdict is a contiguous uint8 CUDA tensor")
+        da = np.asarray(dicts.cpu() if isinstance(dicts, torch.Tensor) else dicts).astype(np.int64).reshape(-1, 2)
+        dict_t = zdict
+    else:
+        parts = [bytes(zdict)] if isinstance(zdict, (bytes, bytearray, memoryview)) else [bytes(b) for b in zdict]
+        lens = np.array([len(b) for b in parts], dtype=np.int64)
+        offs = np.concatenate(([0], np.cumsum(lens)[:-1])) if len(parts) else np.zeros(0, np.int64)
+        da = np.stack([offs, lens], axis=1).astype(np.int64).reshape(-1, 2)
+        dict_t = torch.frombuffer(bytearray(b"".join(parts) or b"\0"), dtype=torch.uint8).to(dev)[:int(lens.sum())]
+    dicts_t = torch.from_numpy(np.ascontiguousarray(da)).to(dev)
+    of_t = None
+    if dict_of is not None:
+        if isinstance(dict_of, torch.Tensor):
+            of = dict_of.cpu().numpy().astype(np.int64).reshape(-1)
+        else:
+            of = np.array([-1 if v is None else int(v) for v in dict_of], dtype=np.int64)
+        if of.shape[0] != n:
+            raise ValueError("dict_of has one entry per stream")
+        of = np.where(of < 0, DMX_BATCH_NODICT, of).astype(np.uint32)
+        of_t = torch.from_numpy(of.view(np.int32).copy()).to(dev)
+    return dict_t, dicts_t, da.shape[0], of_t
+
+
+def inflate_batch(z, streams=None, fmt: str = "auto", sizes=None, strict: bool = True, zdict=None, dict_of=None,
+                  dicts=None):
     """Inflate many independent zlib streams, gzip members or raw DEFLATE streams on the GPU, side
     by side (dmx_inflate_batch_async): z is a list of bytes-like objects, packed into one device
     tensor here, or a contiguous uint8 CUDA tensor with `streams`, an (n, 2) int64 array of
@@ -704,12 +794,20 @@ def inflate_batch(z, streams=None, fmt: str = "auto", sizes=None, strict: bool =
     CUDA tensor, an int64 CUDA tensor of n + 1 with stream k at out[offsets[k]:offsets[k + 1]] (its
     first results[k].out_len bytes), and a numpy structured array of the BResult records (status,
     format, out_len, in_used, check).  strict: a stream with a status raises DeflateError with the
-    status of the lowest such index, which the message names."""
+    status of the lowest such index, which the message names.
+    zdict: preset dictionaries (dmx_inflate_batch_dict_async; RFC 1950 FDICT, zlib's zdict=) -- one
+    bytes-like object, a list of them, or a contiguous uint8 CUDA tensor with `dicts`, an (n, 2) int64
+    array of (off, len) into it.  dict_of: a sequence or tensor with the dictionary index of every
+    stream, -1 or None for none; by default every stream uses dictionary 0.  A zlib stream takes its
+    dictionary where its header has FDICT and names it (else -E_ZPDICT), a raw stream always, a zlib
+    stream without FDICT and a gzip member never.  With zdict=None the call is dmx_inflate_batch_async."""
     import numpy as np
     import torch
     L = lib()
     if fmt not in _BATCH_FMT:
         raise ValueError("fmt is one of " + ", ".join(_BATCH_FMT))
+    if zdict is None and (dict_of is not None or dicts is not None):
+        raise ValueError("dict_of and dicts come with zdict")
     flags = _BATCH_FMT[fmt]
     if isinstance(z, torch.Tensor):
         if streams is None:
@@ -730,7 +828,19 @@ def inflate_batch(z, streams=None, fmt: str = "auto", sizes=None, strict: bool =
     desc[:, :2] = sa
     res = torch.zeros(max(n, 1) * 4, dtype=torch.int64, device=dev)
     st = torch.empty(2, dtype=torch.int64, device=dev)
-    work = torch.empty(int(L.dmx_inflate_batch_work(n)), dtype=torch.uint8, device=dev)
+    if zdict is None:
+        work = torch.empty(int(L.dmx_inflate_batch_work(n)), dtype=torch.uint8, device=dev)
+        what = "dmx_inflate_batch_async"
+
+        def launch(fl, o, ob):
+            return inflate_batch_async(zt, dt, n, fl, o, ob, res, work, st)
+    else:
+        dict_t, dicts_t, nd, of_t = _batch_dicts(zdict, dicts, dict_of, n, dev)
+        work = torch.empty(int(L.dmx_inflate_batch_dict_work(n, nd)), dtype=torch.uint8, device=dev)
+        what = "dmx_inflate_batch_dict_async"
+
+        def launch(fl, o, ob):
+            return inflate_batch_dict_async(zt, dt, n, fl, dict_t, dicts_t, nd, of_t, o, ob, res, work, st)
     measured = None
     if sizes is not None:
         sz = np.asarray(sizes, dtype=np.int64).reshape(-1)
@@ -744,14 +854,14 @@ def inflate_batch(z, streams=None, fmt: str = "auto", sizes=None, strict: bool =
     else:
         desc[:, 3] = -1   # UINT64_MAX: no limit
         dt = torch.from_numpy(desc).to(dev)
-        _check(inflate_batch_async(zt, dt, n, flags | DMX_BATCH_MEASURE, None, 0, res, work, st), "dmx_inflate_batch_async")
+        _check(launch(flags | DMX_BATCH_MEASURE, None, 0), what)
         measured = res.view(max(n, 1), 4)[:n].clone()
         offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
         torch.cumsum(measured[:, 1], 0, out=offsets[1:])
         dt[:, 2], dt[:, 3] = offsets[:-1], measured[:, 1]
         total = int(offsets[-1].item())   # the call's one synchronisation before the decode
     out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-    _check(inflate_batch_async(zt, dt, n, flags, out, total, res, work, st), "dmx_inflate_batch_async")
+    _check(launch(flags, out, total), what)
     rt = res.view(max(n, 1), 4)[:n]
     if measured is not None:
         # a stream the measure pass refused has a window of 0 bytes: its status is the measured one
@@ -1168,7 +1278,8 @@ class Encoder:
 
     def compress_bytes(self, data, sw: int = 32768, max_chain: int = 0, flags: int = DMX_ZLIB, pre=None):
         """Host bytes -> HBM -> encode -> host bytes, on this context (keeps introspection).
-        pre: DMX_F_DICT history of block 0 (host bytes, staged in HBM here)."""
+        pre: DMX_F_DICT history of block 0 (host bytes, staged in HBM here); with DMX_F_FDICT in flags
+        the zlib header names it (1 <= len(pre) <= sw)."""
         import numpy as np
         import torch
         dev = f"cuda:{self.device}"

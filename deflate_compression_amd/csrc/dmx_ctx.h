@@ -39,7 +39,8 @@ struct dmx_ctx {
     uint32_t ncu;     // compute units (the persistent K1 grid of the work-list mode)
     dmx_result* res;
     uint32_t* nfb;        // [0] sort fallbacks of the encode in flight (kernels add, K3's scan reads and zeroes), [1] total,
-                          // [2] the CRC-32 of a DMX_F_GZIP encode's input (dmx_crc.hip writes, K3's scan reads)
+                          // [2] the CRC-32 of a DMX_F_GZIP encode's input (dmx_crc.hip writes, K3's scan reads),
+                          // [3] the DICTID of a DMX_F_FDICT encode (dmx_dict_adler_launch writes, put_header reads)
     uint32_t* crc_rem;    // CRC-32 scratch (dmx_crc.hip): crc_cap span remainders; under DMX_F_BGZF (which
                           // ignores DMX_F_GZIP) the encode's finished CRC-32 per block instead, read by K4
     uint64_t crc_cap;     // spans of DMX_BLK bytes it holds: cap_blocks + 2 (0: no workspace yet)
@@ -106,6 +107,9 @@ DMX_HIDDEN int hip_fail(hipError_t e, const char* what);
 DMX_HIDDEN int dmx_crc32_ranges_launch(const void* d_in, uint64_t n, const dmx_iblock* d_index, uint32_t nblk,
                                        uint32_t* d_crc, const uint32_t* d_want, dmx_inflate_status* d_status,
                                        hipStream_t s);
+// the Adler-32 of d_dict[0, n) into *d_adl, one launch (dmx_inflate_dev.hip: dmx_dict_adler_kernel's
+// arithmetic on one dictionary given by value): the DICTID of a DMX_F_FDICT encode
+DMX_HIDDEN int dmx_dict_adler_launch(const void* d_dict, uint64_t n, uint32_t* d_adl, hipStream_t s);
 // the CRC-32 pass of dmx_inflate_batch_async (dmx_crc.hip): every stream with status 0 and format
 // gzip is finished -- -E_CRC, else the decode's note of a wrong ISIZE as -E_LEN -- and counted in
 // the summary

@@ -586,7 +586,7 @@ extern "C" uint64_t dmx_encode_batch_bound(uint64_t total_in, uint32_t nstreams,
 }
 
 static int eb_flags_ok(uint32_t f) {
-    if (f & (DMX_F_DICT | DMX_F_SPLIT | DMX_F_BGZF)) return 0;
+    if (f & (DMX_F_DICT | DMX_F_SPLIT | DMX_F_BGZF | DMX_F_FDICT)) return 0;
     if (!(f & DMX_F_FINAL)) return 0;
     if (!(f & DMX_F_HEADER) != !(f & DMX_F_TRAILER)) return 0;
     if ((f & DMX_F_GZIP) && !(f & DMX_F_HEADER)) return 0;
@@ -598,7 +598,7 @@ extern "C" int dmx_ctx_reserve_batch(dmx_ctx* c, uint32_t max_blocks, uint32_t m
     if (sw == 0) sw = DMX_BLK;
     if (sw < 1 || sw > DMX_BLK) return -(int)E_RANGE;
     if (max_blocks > 0x7FFFFFFFu || max_streams > 0x7FFFFFFFu) return -(int)E_RANGE;
-    if (flags & (DMX_F_DICT | DMX_F_SPLIT | DMX_F_BGZF)) return -(int)E_INVAL;
+    if (flags & (DMX_F_DICT | DMX_F_SPLIT | DMX_F_BGZF | DMX_F_FDICT)) return -(int)E_INVAL;
     if (max_blocks <= c->cap_blocks && max_blocks <= c->cap_btab && c->bplan && max_streams <= c->cap_bstreams)
         return 0;   // nothing to do: no synchronisation
     HIPCHK(hipSetDevice(c->device));

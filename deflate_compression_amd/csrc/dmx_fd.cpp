@@ -48,6 +48,9 @@ extern "C" int dmx_encode_host(const uint8_t* in, uint64_t n, uint8_t* out, uint
     if (opts) o = *opts;
     if (o.sw == 0) o.sw = DMX_BLK;
     if (o.sw < 1 || o.sw > DMX_BLK) return -(int)E_RANGE;
+    // DMX_F_FDICT names the whole dictionary: one that would be cut to its last sw bytes below is refused
+    // here (the other conditions are dmx_encode_async's)
+    if ((o.flags & DMX_F_FDICT) && o.dict_len > (uint64_t)o.sw) return -(int)E_INVAL;
     const char* dev_s = getenv("DMX_DEVICE");
     const int dev = dev_s ? atoi(dev_s) : 0;
     pthread_mutex_lock(&g_mu);
@@ -619,6 +622,7 @@ static int encode_fd_on(int device, int fd_in, int fd_out, const dmx_opts* opts,
     if (opts) o = *opts;
     if (o.sw == 0) o.sw = DMX_BLK;
     if (o.sw < 1 || o.sw > DMX_BLK) return -(int)E_RANGE;
+    if (o.flags & DMX_F_FDICT) return -(int)E_INVAL;   // (a chunked stream has no caller dictionary to name)
     const uint64_t sw = (uint64_t)o.sw;
     if (chunk < sw) chunk = sw;
     chunk -= chunk % sw;
@@ -960,6 +964,7 @@ extern "C" int dmx_encode_fd_multi(int fd_in, int fd_out, const dmx_opts* opts, 
     if (opts) o = *opts;
     if (o.sw == 0) o.sw = DMX_BLK;
     if (o.sw < 1 || o.sw > DMX_BLK) return -(int)E_RANGE;
+    if (o.flags & DMX_F_FDICT) return -(int)E_INVAL;
     const uint64_t sw = (uint64_t)o.sw;
     if (chunk < sw) chunk = sw;
     chunk -= chunk % sw;

@@ -75,4 +75,45 @@ DMX_GZ_HD static inline int dmx_frame_head(const uint8_t* in, uint64_t n, uint32
     return 0;
 }
 
+// dmx_frame_head for a stream that may come with a preset dictionary (dmx_inflate_batch_dict_async;
+// host twin: tests/c/frame_dict_model.cpp against dmx_inflate_dict_host).  have_dict / dict_adler: whether
+// the caller gave this stream a dictionary, and the Adler-32 of all its bytes.  *primed: the window
+// starts with the dictionary's tail -- a raw stream with a dictionary always (inflateSetDictionary on
+// a raw stream), a zlib stream only where its header has FDICT and its DICTID (RFC 1950 2.2: four
+// bytes behind FLG, most significant first) is dict_adler; then *body is 6.  A zlib stream without
+// FDICT ignores the dictionary, a gzip member has none.  FDICT with the header cut inside the DICTID
+// is -E_ZHEAD (before the dictionary is looked at); FDICT without a dictionary, or with another
+// DICTID, -E_ZPDICT.  Everything else is dmx_frame_head's.  Reads in[0..6) at most, in[0..n) only.
+DMX_GZ_HD static inline int dmx_frame_head_dict(const uint8_t* in, uint64_t n, uint32_t fmt, bool have_dict,
+                                                uint32_t dict_adler, uint32_t* format, uint64_t* body, bool* primed) {
+    *primed = false;
+    *body = 0;
+    *format = fmt == DMX_BATCH_AUTO ? DMX_BATCH_ZLIB : fmt;
+    if (fmt == DMX_BATCH_RAW) {
+        *primed = have_dict;
+        return 0;
+    }
+    if (n < 2) return -(int)E_ZHEAD;
+    const uint32_t cmf = in[0], flg = in[1];
+    const bool magic = cmf == 0x1F && flg == 0x8B;
+    if (fmt == DMX_BATCH_AUTO && magic) *format = DMX_BATCH_GZIP;
+    if (*format == DMX_BATCH_GZIP) {
+        if (!magic) return -(int)E_ZHEAD;
+        return dmx_gz_head(in, n, body);
+    }
+    if ((cmf & 0x0F) != 8) return -(int)E_ZCMPMT;
+    if ((cmf >> 4) > 7) return -(int)E_ZSLWIN;
+    if (((cmf << 8) | flg) % 31) return -(int)E_ZFCHCK;
+    if (!(flg & 0x20)) {
+        *body = 2;
+        return 0;
+    }
+    if (n < 6) return -(int)E_ZHEAD;
+    const uint32_t dictid = ((uint32_t)in[2] << 24) | ((uint32_t)in[3] << 16) | ((uint32_t)in[4] << 8) | (uint32_t)in[5];
+    if (!have_dict || dictid != dict_adler) return -(int)E_ZPDICT;
+    *body = 6;
+    *primed = true;
+    return 0;
+}
+
 #endif

@@ -316,6 +316,45 @@ static long gzip_header(const uint8_t* in, size_t n, size_t* body) {
     return 0;
 }
 
+/* The blocks of a stream from the reader's position until BFINAL; shared by deflate_decompress and
+ * dmx_inflate_dict_host.  Returns 0 or the status of the first block that fails. */
+static int inflate_blocks(ist* s) {
+    int last, r = 0;
+    do {
+        last = bits(s, 1);
+        int type = bits(s, 2);
+        if (s->err) { r = s->err; break; }
+        if (type == 0) r = stored(s);
+        else if (type == 1) r = fixed(s);
+        else if (type == 2) r = dynamic(s);
+        else r = -(int)E_ZBTYPE;
+        if (r) break;
+    } while (!last);
+    return r;
+}
+
+/* The trailer behind the last block, for the output o[0, on): the partial byte is dropped; then gzip's
+ * CRC-32 and ISIZE, little-endian (a trailer cut short is -E_CRC, the CRC is checked first), or
+ * zlib's big-endian Adler-32 (-E_ZADL32, cut short too).  Bytes after the trailer are ignored. */
+static int inflate_trailer(ist* s, int gz, const uint8_t* o, size_t on) {
+    s->bitbuf >>= s->bitcnt & 7;
+    s->bitcnt -= s->bitcnt & 7;
+    if (gz) {
+        uint32_t want = 0, isize = 0;
+        for (int k = 0; k < 4; k++) want |= (uint32_t)bits(s, 8) << (8 * k);
+        for (int k = 0; k < 4; k++) isize |= (uint32_t)bits(s, 8) << (8 * k);
+        if (s->err) return -(int)E_CRC;
+        if (want != dmx_crc32_host(0, o, on)) return -(int)E_CRC;
+        if (isize != (uint32_t)on) return -(int)E_LEN;
+        return 0;
+    }
+    uint32_t want = 0;
+    for (int k = 0; k < 4; k++) want = (want << 8) | (uint32_t)bits(s, 8);
+    if (s->err) return -(int)E_ZADL32;
+    if (want != adler32(o, on)) return -(int)E_ZADL32;
+    return 0;
+}
+
 int deflate_decompress(struct string_len* decompr_dat, struct string_len* compr_dat, int ops) {
     if (!decompr_dat || !compr_dat || (!compr_dat->str && compr_dat->len)) return -E_INVAL;
     ist s;
@@ -339,37 +378,8 @@ int deflate_decompress(struct string_len* decompr_dat, struct string_len* compr_
         if (flg & 0x20) return -(int)E_ZPDICT;
         s.pos = 2;
     }
-    int last, r = 0;
-    do {
-        last = bits(&s, 1);
-        int type = bits(&s, 2);
-        if (s.err) { r = s.err; break; }
-        if (type == 0) r = stored(&s);
-        else if (type == 1) r = fixed(&s);
-        else if (type == 2) r = dynamic(&s);
-        else r = -(int)E_ZBTYPE;
-        if (r) break;
-    } while (!last);
-    if (!r && gz) {
-        /* drop the partial byte, then CRC-32 and ISIZE, little-endian; a trailer cut short
-         * is -E_CRC; bytes after the member are ignored */
-        s.bitbuf >>= s.bitcnt & 7;
-        s.bitcnt -= s.bitcnt & 7;
-        uint32_t want = 0, isize = 0;
-        for (int k = 0; k < 4; k++) want |= (uint32_t)bits(&s, 8) << (8 * k);
-        for (int k = 0; k < 4; k++) isize |= (uint32_t)bits(&s, 8) << (8 * k);
-        if (s.err) r = -(int)E_CRC;
-        else if (want != dmx_crc32_host(0, s.out, s.olen)) r = -(int)E_CRC;
-        else if (isize != (uint32_t)s.olen) r = -(int)E_LEN;
-    } else if (!r) {
-        /* drop the partial byte, then the big-endian Adler-32 */
-        s.bitbuf >>= s.bitcnt & 7;
-        s.bitcnt -= s.bitcnt & 7;
-        uint32_t want = 0;
-        for (int k = 0; k < 4; k++) want = (want << 8) | (uint32_t)bits(&s, 8);
-        if (s.err) r = -(int)E_ZADL32;
-        else if (want != adler32(s.out, s.olen)) r = -(int)E_ZADL32;
-    }
+    int r = inflate_blocks(&s);
+    if (!r) r = inflate_trailer(&s, gz, s.out, s.olen);
     if (r) {
         free(s.out);
         return r;
@@ -381,6 +391,83 @@ int deflate_decompress(struct string_len* decompr_dat, struct string_len* compr_
     if (ops & DEFLATE_NULLTERM) s.out[s.olen] = 0;  /* buffer always has one spare byte */
     decompr_dat->str = s.out;
     decompr_dat->len = s.olen;
+    return 0;
+}
+
+/* One stream of dmx_inflate_batch_dict_async on the host (include/dmx.h): the framing under fmt
+ * (DMX_BATCH_*), a preset dictionary where the stream takes one -- a raw stream always, a zlib
+ * stream whose header has FDICT and whose DICTID is the Adler-32 of all dict_len bytes -- and the
+ * trailer.  The dictionary's last min(dict_len, 32768) bytes are put in front of the output, so a
+ * distance reaches them as it reaches earlier output, and are taken off at the end; the trailer's
+ * check covers the output alone.  deflate_decompress's statuses, and -E_ZPDICT for FDICT without a
+ * dictionary or with another DICTID, -E_ZHEAD for a header cut inside the DICTID. */
+int dmx_inflate_dict_host(const void* z, uint64_t n, uint32_t fmt, const void* dict, uint64_t dict_len, void** out,
+                          uint64_t* out_len, uint64_t* in_used) {
+    if (!out || !out_len || (!z && n) || (!dict && dict_len) || fmt > DMX_BATCH_RAW) return -(int)E_INVAL;
+    *out = NULL;
+    *out_len = 0;
+    if (in_used) *in_used = 0;
+    ist s;
+    memset(&s, 0, sizeof(s));
+    s.in = (const uint8_t*)z;
+    s.n = (size_t)n;
+    uint32_t format = fmt == DMX_BATCH_AUTO ? DMX_BATCH_ZLIB : fmt;
+    int primed = 0;
+    if (fmt == DMX_BATCH_RAW) {
+        primed = dict != NULL;
+    } else {
+        if (s.n < 2) return -(int)E_ZHEAD;
+        const int cmf = s.in[0], flg = s.in[1];
+        const int magic = cmf == 0x1F && flg == 0x8B;
+        if (fmt == DMX_BATCH_AUTO && magic) format = DMX_BATCH_GZIP;
+        if (format == DMX_BATCH_GZIP) {
+            if (!magic) return -(int)E_ZHEAD;
+            size_t body = 0;
+            const long e = gzip_header(s.in, s.n, &body);
+            if (e) return (int)e;
+            s.pos = body;
+        } else {
+            if ((cmf & 0x0F) != 8) return -(int)E_ZCMPMT;
+            if ((cmf >> 4) > 7) return -(int)E_ZSLWIN;
+            if (((cmf << 8) | flg) % 31) return -(int)E_ZFCHCK;
+            s.pos = 2;
+            if (flg & 0x20) {
+                if (s.n < 6) return -(int)E_ZHEAD;
+                const uint32_t id = ((uint32_t)s.in[2] << 24) | ((uint32_t)s.in[3] << 16) | ((uint32_t)s.in[4] << 8) | s.in[5];
+                if (!dict || id != adler32((const uint8_t*)dict, (size_t)dict_len)) return -(int)E_ZPDICT;
+                s.pos = 6;
+                primed = 1;
+            }
+        }
+    }
+    const size_t dl = primed ? (size_t)(dict_len < DMX_BLK ? dict_len : DMX_BLK) : 0;
+    int r = 0;
+    if (dl) {
+        s.ocap = dl + (1 << 16);
+        s.out = (uint8_t*)malloc(s.ocap + 1);
+        if (!s.out) return -E_MALLOC;
+        memcpy(s.out, (const uint8_t*)dict + (dict_len - dl), dl);
+        s.olen = dl;
+    }
+    r = inflate_blocks(&s);
+    if (!r && format == DMX_BATCH_RAW) {   /* a raw stream ends at the next byte: no trailer */
+        s.bitbuf >>= s.bitcnt & 7;
+        s.bitcnt -= s.bitcnt & 7;
+    } else if (!r) {                       /* the check covers the output alone */
+        r = inflate_trailer(&s, format == DMX_BATCH_GZIP, s.out ? s.out + dl : NULL, s.olen - dl);
+    }
+    if (r) {
+        free(s.out);
+        return r;
+    }
+    if (!s.out) {
+        s.out = (uint8_t*)malloc(1);
+        if (!s.out) return -E_MALLOC;
+    }
+    if (dl) memmove(s.out, s.out + dl, s.olen - dl);
+    *out = s.out;
+    *out_len = s.olen - dl;
+    if (in_used) *in_used = (uint64_t)s.pos - (uint64_t)(s.bitcnt / 8);
     return 0;
 }
 

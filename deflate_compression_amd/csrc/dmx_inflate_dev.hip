@@ -963,13 +963,126 @@ __global__ void dmx_inflate_batch_clear_kernel(IBatchCtl* __restrict__ ctl, dmx_
     st->total_out = 0;
 }
 
-template <bool MEASURE>
+// Preset dictionaries (dmx_inflate_batch_dict_async; DICT).  A dictionary is output that was flushed
+// before the stream began: its last dlen <= IW bytes go to win[0, dlen), the stream starts with
+// op = fl = dlen, base = out_off - dlen (the first flushed byte lands at out_off; Adler-32 is folded
+// over flushed bytes only) and cap = out_cap + dlen, and reports ob + op - dlen.  Nothing below that
+// level knows: the too-far test is dist > op while ob == 0, the ring invariant, isym_run, the stored
+// copy and the renormalisation see positions only, and with W == IW no distance exceeds the ring
+// (dlen == IW fills it exactly; a first match at distance IW reads the slot it is about to write, as
+// such a match does mid-stream).  A stream without a dictionary starts at op = 0 as before, so what
+// the ring held for the stream before it -- primed bytes included -- is never read.
+struct IBatchDict {   // by value; all zero (no dictionaries) for the instantiations without DICT
+    const uint8_t* dict;       // d_dict
+    uint64_t dict_bytes;
+    const dmx_bdict* dicts;
+    const uint32_t* dict_of;   // NULL: every stream uses dictionary 0
+    const uint32_t* adler;     // in d_work: the Adler-32 of every dictionary (dmx_dict_adler_kernel)
+    uint32_t ndicts;
+};
+
+// win[0, n) = src[0, n), n <= IW: 16-byte loads of the aligned groups inside the range, single bytes
+// at its edges (no byte outside src[0, n) is loaded); everything is wave-uniform but the lane's share
+__device__ __forceinline__ void iprime(uint8_t* win, const uint8_t* src, uint32_t n, uint32_t lane) {
+    const uint32_t head = min(n, (uint32_t)((16 - ((uintptr_t)src & 15)) & 15));
+    if (lane < head) win[lane] = src[lane];
+    const uint32_t groups = (n - head) >> 4;
+    for (uint32_t g = lane; g < groups; g += 64) {
+        const uint32_t p = head + 16 * g;
+        const uint4 v = *reinterpret_cast<const uint4*>(src + p);
+        if (head == 0) {
+            *reinterpret_cast<uint4*>(win + p) = v;
+        } else if ((head & 3) == 0) {
+            uint32_t* w = reinterpret_cast<uint32_t*>(win + p);
+            w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+        } else {
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int j = 0; j < 16; j++) win[p + j] = (uint8_t)(w[j >> 2] >> (8 * (j & 3)));
+        }
+    }
+    const uint32_t tail = head + 16 * groups;   // fewer than 16 bytes behind the last group
+    if (lane < n - tail) win[tail + lane] = src[tail + lane];
+    __syncthreads();
+}
+
+// The Adler-32 of every dictionary of a call into adl[j] (0 for an entry outside the buffer: the
+// decode refuses it before it looks), one block of 256 threads per dictionary.  A thread takes a
+// slice whose edges are 16-byte aligned addresses and folds it in pieces of at most 4 096 bytes
+// with position-weighted sums, as io_flush does (a' = a + S, b' = b + n a + T mod 65521, from
+// a = b = 0); the slices combine by the same rule, and the leading 1 of Adler-32 adds len to b.
+// the Adler-32 of src[0, n) into *adl, by the 256 threads of one block
+__device__ __forceinline__ void dict_adler_block(const uint8_t* src, uint64_t n, uint32_t* adl) {
+    __shared__ uint32_t sa[256], sb[256];
+    constexpr uint32_t M = 65521u;
+    const uint32_t t = threadIdx.x;
+    const uintptr_t p = (uintptr_t)src, a0 = p & ~(uintptr_t)15;
+    const uint8_t* q = reinterpret_cast<const uint8_t*>(a0);   // positions below are relative to a0
+    const uint64_t pb = p - a0, pe = pb + n;
+    const uint64_t sl = ((pe + 255) / 256 + 15) & ~15ull;
+    uint64_t lo = (uint64_t)t * sl, hi = lo + sl;
+    if (lo < pb) lo = pb;
+    if (hi > pe) hi = pe;
+    uint32_t a = 0, b = 0;
+    for (uint64_t i = lo; i < hi;) {
+        const uint64_t ce = hi - i > 4096 ? i + 4096 : hi;
+        uint32_t cs = 0;
+        uint64_t ct = 0;   // <= 4096 * 4096 * 255
+        uint64_t x = i;
+        for (; x < ce && (x & 15); x++) { cs += q[x]; ct += (ce - x) * q[x]; }
+        for (; x + 16 <= ce; x += 16) {
+            const uint4 v = *reinterpret_cast<const uint4*>(q + x);
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int k = 0; k < 16; k++) {
+                const uint32_t c = (w[k >> 2] >> (8 * (k & 3))) & 0xFFu;
+                cs += c;
+                ct += (ce - x - k) * c;
+            }
+        }
+        for (; x < ce; x++) { cs += q[x]; ct += (ce - x) * q[x]; }
+        b = (uint32_t)((b + (ce - i) * a + ct % M) % M);
+        a = (a + cs) % M;
+        i = ce;
+    }
+    // the slice's share of the whole: its bytes are added to b once more for every byte behind it
+    sa[t] = a;
+    sb[t] = lo < hi ? (uint32_t)((b + ((pe - hi) % M) * a) % M) : 0u;
+    __syncthreads();
+    if (t == 0) {
+        uint64_t A = 1, B = n % M;
+        for (int k = 0; k < 256; k++) { A += sa[k]; B += sb[k]; }
+        *adl = ((uint32_t)(B % M) << 16) | (uint32_t)(A % M);
+    }
+}
+__global__ __launch_bounds__(256) void dmx_dict_adler_kernel(const uint8_t* __restrict__ dict, uint64_t dict_bytes,
+                                                             const dmx_bdict* __restrict__ dicts,
+                                                             uint32_t* __restrict__ adl) {
+    const uint32_t j = blockIdx.x;
+    const uint64_t off = dicts[j].off, n = dicts[j].len;
+    if (off > dict_bytes || n > dict_bytes - off) {   // (uniform)
+        if (threadIdx.x == 0) adl[j] = 0;
+        return;
+    }
+    dict_adler_block(dict + off, n, adl + j);
+}
+// one dictionary given by value: the DICTID of a DMX_F_FDICT encode (dmx_encode_async, dmx_kernels.hip)
+__global__ __launch_bounds__(256) void dmx_dict_adler_one_kernel(const uint8_t* __restrict__ dict, uint64_t n,
+                                                                 uint32_t* __restrict__ adl) {
+    dict_adler_block(dict, n, adl);
+}
+int dmx_dict_adler_launch(const void* d_dict, uint64_t n, uint32_t* d_adl, hipStream_t s) {
+    hipLaunchKernelGGL(dmx_dict_adler_one_kernel, dim3(1), dim3(256), 0, s, (const uint8_t*)d_dict, n, d_adl);
+    return hipGetLastError() == hipSuccess ? 0 : -(int)E_DEVICE;
+}
+
+template <bool MEASURE, bool DICT = false>
 __global__ __launch_bounds__(64) void dmx_inflate_batch_kernel(const uint8_t* __restrict__ z, uint64_t zbytes,
                                                                const dmx_bstream* __restrict__ streams, uint32_t nstreams,
                                                                uint32_t fmt, uint8_t* out, uint64_t out_bytes,
                                                                dmx_bresult* __restrict__ res, uint32_t* __restrict__ gtab,
                                                                IBatchCtl* __restrict__ ctl,
-                                                               dmx_batch_status* __restrict__ st) {
+                                                               dmx_batch_status* __restrict__ st, const IBatchDict dd) {
     __shared__ InfLDS<IW> S;   // the kernel's one __shared__ object: isym_run addresses the ring from LDS 0
     uint32_t* gt = gtab + (uint64_t)blockIdx.x * ITAB_WORDS;
     const uint32_t lane = threadIdx.x;
@@ -988,7 +1101,38 @@ __global__ __launch_bounds__(64) void dmx_inflate_batch_kernel(const uint8_t* __
         if (in_off > zbytes || in_len > zbytes - in_off || in_len > 0xFFFFFFF0ull) err = -(int)E_RANGE;
         if (!MEASURE && (out_off > out_bytes || out_cap > out_bytes - out_off)) err = -(int)E_RANGE;
         const uint8_t* zs = z + in_off;
-        if (!err) err = dmx_frame_head(zs, in_len, fmt, &format, &body);
+        uint32_t dlen = 0;   // primed bytes (DICT)
+        if constexpr (DICT) {
+            // the stream's dictionary: its index, its range, its check value -- all wave-uniform
+            const uint32_t di = rfl(dd.dict_of ? dd.dict_of[k] : dd.ndicts ? 0u : DMX_BATCH_NODICT);
+            const uint8_t* dsrc = nullptr;
+            uint32_t dadl = 0, dl = 0;
+            bool have = false;
+            if (!err && di != DMX_BATCH_NODICT) {
+                if (di >= dd.ndicts) {
+                    err = -(int)E_RANGE;
+                } else {
+                    const uint64_t doff = rfl64(dd.dicts[di].off), dn = rfl64(dd.dicts[di].len);
+                    if (doff > dd.dict_bytes || dn > dd.dict_bytes - doff) {
+                        err = -(int)E_RANGE;
+                    } else {
+                        have = true;
+                        dadl = rfl(dd.adler[di]);
+                        dl = dn < IW ? (uint32_t)dn : (uint32_t)IW;
+                        dsrc = dd.dict + doff + (dn - dl);
+                    }
+                }
+            }
+            bool primed = false;
+            if (!err) err = dmx_frame_head_dict(zs, in_len, fmt, have, dadl, &format, &body, &primed);
+            err = (int)rfl((uint32_t)err);
+            if (!err && rfl(primed ? 1u : 0u)) {
+                dlen = dl;
+                iprime(S.win, dsrc, dlen, lane);
+            }
+        } else {
+            if (!err) err = dmx_frame_head(zs, in_len, fmt, &format, &body);
+        }
         format = rfl(format);
         body = rfl64(body);
         err = (int)rfl((uint32_t)err);
@@ -998,11 +1142,15 @@ __global__ __launch_bounds__(64) void dmx_inflate_batch_kernel(const uint8_t* __
         for (int q = 0; q < INF_NST; q++) o.st[q] = 0;
 #endif
         o.out = out;
-        o.base = MEASURE ? 0 : out_off;
+        // base lies below the window by the primed bytes.  The unsigned subtraction wraps when out_off <
+        // dlen (always under MEASURE, where it is 0 - dlen on a NULL out): that is meant.  out + base is
+        // only ever used with a position p >= fl >= dlen added (io_flush's dst + p), which is back inside
+        // the window; the run's far-source base (gpos0) is dead code with W == IW.  Do not clamp it.
+        o.base = (MEASURE ? 0 : out_off) - dlen;
         o.ob = 0;
-        o.cap = out_cap;
-        o.op = 0;
-        o.fl = 0;
+        o.cap = out_cap > ~0ull - dlen ? ~0ull : out_cap + dlen;
+        o.op = dlen;
+        o.fl = dlen;
         o.a = 1;
         o.b = 0;
         if (!err) {
@@ -1021,7 +1169,7 @@ __global__ __launch_bounds__(64) void dmx_inflate_batch_kernel(const uint8_t* __
             r.wi = rfl(r.wi);
             r.bc = rfl(r.bc);
             io_flush<true, !MEASURE>(S, o, o.op, lane);
-            olen = o.ob + o.op;
+            olen = o.ob + o.op - dlen;
             ib_drop(r, r.bc & 7);   // the trailer starts at the next byte; a raw stream ends there
             // in_used from the reader's position here, in front of the three-way branch, plus the
             // trailer's size: taken from the reader behind the branch (ib_bytepos), the raw path's
@@ -1187,7 +1335,7 @@ static uint32_t ibatch_resident(void) {
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= ITAB_DEVS) return 0;
     uint32_t v = __atomic_load_n(&wg[dev], __ATOMIC_RELAXED);
     if (v) return v;
-    // (both instantiations have the same LDS, the limit; the decode's registers are no fewer)
+    // (all four instantiations have the same LDS, the limit, and one wave per SIMD fits their registers)
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, dmx_inflate_batch_kernel<false>, 64, 0) != hipSuccess ||
         hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || per < 1 || ncu < 1)
         return 0;
@@ -1216,12 +1364,60 @@ extern "C" int dmx_inflate_batch_async(const void* d_z, uint64_t zbytes, const d
     const uint32_t resident = ibatch_resident();
     if (!resident) return -(int)E_DEVICE;
     const uint32_t grid = nstreams < resident ? nstreams : resident;
+    const IBatchDict none = {nullptr, 0, nullptr, nullptr, nullptr, 0};
     if (measure)
         hipLaunchKernelGGL(dmx_inflate_batch_kernel<true>, dim3(grid), dim3(64), 0, s, (const uint8_t*)d_z, zbytes, d_streams,
-                           nstreams, fmt, (uint8_t*)nullptr, 0ull, d_results, gtab, ctl, d_status);
+                           nstreams, fmt, (uint8_t*)nullptr, 0ull, d_results, gtab, ctl, d_status, none);
     else
         hipLaunchKernelGGL(dmx_inflate_batch_kernel<false>, dim3(grid), dim3(64), 0, s, (const uint8_t*)d_z, zbytes, d_streams,
-                           nstreams, fmt, (uint8_t*)d_out, out_bytes, d_results, gtab, ctl, d_status);
+                           nstreams, fmt, (uint8_t*)d_out, out_bytes, d_results, gtab, ctl, d_status, none);
+    if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
+    if (measure || fmt == DMX_BATCH_ZLIB || fmt == DMX_BATCH_RAW) return 0;   // no gzip member to finish
+    return dmx_crc32_batch_launch(d_out, out_bytes, d_streams, nstreams, d_results, d_status, s);
+}
+
+// The same with preset dictionaries.  d_work: dmx_inflate_batch_work(nstreams) bytes as above, then
+// one Adler-32 word per dictionary (rounded up to 256 bytes), so the tables lie where they lay.
+extern "C" uint64_t dmx_inflate_batch_dict_work(uint32_t nstreams, uint32_t ndicts) {
+    return dmx_inflate_batch_work(nstreams) + ((4ull * ndicts + 255) & ~255ull);
+}
+
+extern "C" int dmx_inflate_batch_dict_async(const void* d_z, uint64_t zbytes, const dmx_bstream* d_streams, uint32_t nstreams,
+                                            uint32_t flags, const void* d_dict, uint64_t dict_bytes,
+                                            const dmx_bdict* d_dicts, uint32_t ndicts, const uint32_t* d_dict_of,
+                                            void* d_out, uint64_t out_bytes, dmx_bresult* d_results, void* d_work,
+                                            uint64_t work_bytes, dmx_batch_status* d_status, void* stream) {
+    const bool measure = (flags & DMX_BATCH_MEASURE) != 0;
+    if (!d_results || !d_status || !d_work || (!d_streams && nstreams) || (!d_z && zbytes) || (!d_out && !measure) ||
+        (!d_dicts && ndicts) || (!d_dict && dict_bytes))
+        return -(int)E_INVAL;
+    if (((uintptr_t)d_streams & 7) || ((uintptr_t)d_results & 7) || ((uintptr_t)d_status & 7) || ((uintptr_t)d_dicts & 7) ||
+        ((uintptr_t)d_dict_of & 3))
+        return -(int)E_INVAL;
+    if (((uintptr_t)d_work & 255) || work_bytes < dmx_inflate_batch_dict_work(nstreams, ndicts)) return -(int)E_INVAL;
+    const uint32_t fmt = flags & 15u;
+    if ((flags & ~(15u | DMX_BATCH_MEASURE)) || fmt > DMX_BATCH_RAW) return -(int)E_RANGE;
+    hipStream_t s = (hipStream_t)stream;
+    IBatchCtl* ctl = (IBatchCtl*)d_work;
+    uint32_t* gtab = (uint32_t*)((uint8_t*)d_work + 256);
+    uint32_t* adl = (uint32_t*)((uint8_t*)d_work + dmx_inflate_batch_work(nstreams));
+    hipLaunchKernelGGL(dmx_inflate_batch_clear_kernel, dim3(1), dim3(1), 0, s, ctl, d_status);
+    if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
+    if (!nstreams) return 0;
+    const uint32_t resident = ibatch_resident();
+    if (!resident) return -(int)E_DEVICE;
+    if (ndicts) {
+        hipLaunchKernelGGL(dmx_dict_adler_kernel, dim3(ndicts), dim3(256), 0, s, (const uint8_t*)d_dict, dict_bytes, d_dicts, adl);
+        if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
+    }
+    const uint32_t grid = nstreams < resident ? nstreams : resident;
+    const IBatchDict dd = {(const uint8_t*)d_dict, dict_bytes, d_dicts, d_dict_of, adl, ndicts};
+    if (measure)
+        hipLaunchKernelGGL((dmx_inflate_batch_kernel<true, true>), dim3(grid), dim3(64), 0, s, (const uint8_t*)d_z, zbytes,
+                           d_streams, nstreams, fmt, (uint8_t*)nullptr, 0ull, d_results, gtab, ctl, d_status, dd);
+    else
+        hipLaunchKernelGGL((dmx_inflate_batch_kernel<false, true>), dim3(grid), dim3(64), 0, s, (const uint8_t*)d_z, zbytes,
+                           d_streams, nstreams, fmt, (uint8_t*)d_out, out_bytes, d_results, gtab, ctl, d_status, dd);
     if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
     if (measure || fmt == DMX_BATCH_ZLIB || fmt == DMX_BATCH_RAW) return 0;   // no gzip member to finish
     return dmx_crc32_batch_launch(d_out, out_bytes, d_streams, nstreams, d_results, d_status, s);

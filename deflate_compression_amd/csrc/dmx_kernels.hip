@@ -2282,10 +2282,11 @@ __device__ __forceinline__ bool wl_skip(uint32_t x, uint32_t M, uint32_t nblk) {
 // there are none.  Nothing after K0 may write there: the apply launch zeroes the words the
 // other blocks share around that range byte by byte (zero_word_keep).
 // The container's framing widths: the zlib header 78 9C (16 bits) and big-endian Adler-32
-// (32), or with DMX_F_GZIP the 10-byte gzip header (80) and CRC-32 + ISIZE (64).  80 = 16 mod 32,
-// so the first block starts at the same bit of a word in both, two words later.
+// (32), or with DMX_F_GZIP the 10-byte gzip header (80) and CRC-32 + ISIZE (64), or with DMX_F_FDICT
+// the zlib header with its DICTID (48).  80 = 48 = 16 mod 32, so the first block starts at the same
+// bit of a word in all three, one or two words later.
 __host__ __device__ __forceinline__ uint32_t hdr_bits(uint32_t flags) {
-    return !(flags & DMX_F_HEADER) ? 0u : (flags & DMX_F_GZIP) ? 80u : 16u;
+    return !(flags & DMX_F_HEADER) ? 0u : (flags & DMX_F_GZIP) ? 80u : (flags & DMX_F_FDICT) ? 48u : 16u;
 }
 __host__ __device__ __forceinline__ uint32_t trl_bits(uint32_t flags) {
     return !(flags & DMX_F_TRAILER) ? 0u : (flags & DMX_F_GZIP) ? 64u : 32u;
@@ -4563,12 +4564,19 @@ __device__ __forceinline__ void gor_bits(uint32_t* out32, uint64_t pos, uint32_t
 // The container header: zlib 78 9C (bits 0..15), or gzip 1F 8B 08 00, mtime 0, XFL 0, OS 255
 // (bits 0..79).  The gzip header owns words 0 and 1 (plain stores: nothing else writes them) and
 // shares word 2 with the first block, as the zlib header shares word 0 (zeroed by the scan).
-__device__ __forceinline__ void put_header(uint32_t* out32, uint32_t flags) {
+// DMX_F_FDICT: 78 BB and the DICTID, most significant byte first (bits 0..47); dictid[0] is the
+// dictionary's Adler-32.  The header owns word 0 (a plain store) and shares word 1, which the scan
+// zeroed as the first block's first word, with that block.
+__device__ __forceinline__ void put_header(uint32_t* out32, uint32_t flags, const uint32_t* dictid = nullptr) {
     if (!(flags & DMX_F_HEADER)) return;
     if (flags & DMX_F_GZIP) {
         out32[0] = 0x00088B1Fu;
         out32[1] = 0u;
         gor_bits(out32, 64, 0xFF00u, 16);
+    } else if (flags & DMX_F_FDICT) {
+        const uint32_t id = dictid[0];
+        out32[0] = 0xBB78u | ((id >> 24) << 16) | (((id >> 16) & 0xFFu) << 24);
+        gor_bits(out32, 32, ((id >> 8) & 0xFFu) | ((id & 0xFFu) << 8), 16);
     } else {
         gor_bits(out32, 0, 0x9C78u, 16);
     }
@@ -4629,13 +4637,14 @@ __device__ __forceinline__ uint32_t tail_bits(uint32_t flags) {
 // Adler-32, or with DMX_F_GZIP little-endian CRC-32 and input length n mod 2^32; `adler` is
 // the stream's check value, either one); T = end of the last block, end = byte-aligned end of the DEFLATE data.
 __device__ __forceinline__ void stream_framing(uint32_t* out32, uint32_t flags, uint32_t nblk, uint64_t T,
-                                               uint64_t end, uint32_t adler, uint64_t n) {
+                                               uint64_t end, uint32_t adler, uint64_t n,
+                                               const uint32_t* dictid = nullptr) {
     if (flags & DMX_F_BGZF) {   // (T == end: behind the last member, or 0)
         if (flags & DMX_F_FINAL) bgzf_put_eof(out32, end);
         return;
     }
     const uint64_t start = hdr_bits(flags);
-    put_header(out32, flags);
+    put_header(out32, flags, dictid);
     if (nblk == 0 && (flags & DMX_F_FINAL)) gor_bits(out32, start, 3u, 3);  // BFINAL=1, BTYPE=01, EOB=0000000
     if (!(flags & DMX_F_FINAL) && nblk > 0) gor_bits(out32, align8(T + 3) + 16, 0xFFFFu, 16);  // sync flush
     if ((flags & DMX_F_TRAILER) && (flags & DMX_F_GZIP)) {
@@ -4975,7 +4984,7 @@ __global__ __launch_bounds__(ST) void dmx_scan_kernel(ScanTile* __restrict__ til
     if (nblk == 0) {   // no pack launch: the whole stream is written here
         if (tid <= (start >> 5) && start) out32[tid] = 0;   // every word the header touches (T >> 5 is at or past the last)
         __syncthreads();
-        if (tid == 0) stream_framing(out32, flags, 0, ext.T, ext.end, check, n);
+        if (tid == 0) stream_framing(out32, flags, 0, ext.T, ext.end, check, n, nfallback + 3);   // ([3]: DMX_F_FDICT's DICTID)
     }
 }
 
@@ -5086,8 +5095,8 @@ __device__ __forceinline__ void st_or64(uint32_t* st, uint32_t pos, uint64_t v, 
 // The first block writes the container header, the last one the sync flush / trailer (the
 // scan zeroed the words they share with a block; every write into those is an atomicOr).
 __device__ __forceinline__ void pack_framing(uint32_t* out32, uint32_t flags, uint32_t nblk, uint32_t b,
-                                             const dmx_result* res) {
-    if (b == 0) put_header(out32, flags);
+                                             const dmx_result* res, const uint32_t* dictid) {
+    if (b == 0) put_header(out32, flags, dictid);
     if (b == nblk - 1) {
         const uint64_t T = res->end_bits;
         stream_framing(out32, flags & ~DMX_F_HEADER, nblk, T, stream_end(flags, nblk, T), res->adler, res->n);
@@ -5193,7 +5202,7 @@ __device__ __forceinline__ void pack_one(const uint32_t b, const uint8_t* __rest
             put_word(k, gen_word(k));
         }
         if constexpr (!BATCH)
-            if (tid == 0 && (b == 0 || b == nblk - 1)) pack_framing(out32, flags, nblk, b, res);
+            if (tid == 0 && (b == 0 || b == nblk - 1)) pack_framing(out32, flags, nblk, b, res, bcrc);
         return;
     }
     // coded blocks: the bits go through an 8 KB LDS ring (PK_RING words) that is flushed to
@@ -5350,7 +5359,7 @@ __device__ __forceinline__ void pack_one(const uint32_t b, const uint8_t* __rest
     __syncthreads();
     for (uint32_t k = tid; base + k < nwords; k += PT) out_word(base + k, stage[k]);
     if constexpr (!BATCH)
-        if (tid == 0 && (b == 0 || b == nblk - 1)) pack_framing(out32, flags, nblk, b, res);
+        if (tid == 0 && (b == 0 || b == nblk - 1)) pack_framing(out32, flags, nblk, b, res, bcrc);
 }
 
 // K4: one workgroup per block (wl == nullptr), or a grid that strides over the apply
@@ -5450,7 +5459,8 @@ extern "C" uint64_t dmx_max_compressed(uint64_t n, int32_t sw) {
     const uint64_t nblk = (n + (uint64_t)sw - 1) / (uint64_t)sw;
     return ((n + 5 * nblk + 2 + 4 + 5 + 16) + 3) & ~3ull;
 }
-// the same for a container: DMX_F_GZIP frames with 18 bytes (10 + 8) where zlib has 6 (2 + 4)
+// the same for a container: DMX_F_GZIP frames with 18 bytes (10 + 8) where zlib has 6 (2 + 4),
+// DMX_F_FDICT with 10 (the DICTID)
 // DMX_F_BGZF: 26 bytes (18 + 8) around every block and the 28-byte end-of-file member
 extern "C" uint64_t dmx_max_compressed_flags(uint64_t n, int32_t sw, uint32_t flags) {
     if (flags & DMX_F_BGZF) {
@@ -5458,7 +5468,7 @@ extern "C" uint64_t dmx_max_compressed_flags(uint64_t n, int32_t sw, uint32_t fl
         const uint64_t nblk = (n + (uint64_t)sw - 1) / (uint64_t)sw;
         return dmx_max_compressed(n, sw) + 26 * nblk + 28;
     }
-    return dmx_max_compressed(n, sw) + ((flags & DMX_F_GZIP) ? 12u : 0u);
+    return dmx_max_compressed(n, sw) + ((flags & DMX_F_GZIP) ? 12u : (flags & DMX_F_FDICT) ? 4u : 0u);
 }
 
 static void ctx_free_ws(dmx_ctx* c) {
@@ -5715,6 +5725,12 @@ extern "C" int dmx_encode_async(dmx_ctx* c, const void* d_in, uint64_t n, void* 
     if (o.max_chain < 0) return -(int)E_RANGE;
     if (o.deep_chain < 0 || o.deep_chain > 255) return -(int)E_RANGE;
     if ((reinterpret_cast<uintptr_t>(d_out) & 3) != 0) return -(int)E_INVAL;
+    // DMX_F_FDICT: the header names the dictionary, so there is one, whole (the DICTID covers what
+    // the parse may reference), and the container is zlib's
+    if ((o.flags & DMX_F_FDICT) &&
+        (!(o.flags & DMX_F_DICT) || !(o.flags & DMX_F_HEADER) || (o.flags & (DMX_F_GZIP | DMX_F_BGZF)) || !o.dict ||
+         o.dict_len < 1 || o.dict_len > (uint64_t)o.sw))
+        return -(int)E_INVAL;
     // DMX_F_BGZF: members are independent (no DMX_F_DICT) and hold one DEFLATE block (no DMX_F_SPLIT
     // so far); every member frames itself, so the stream's own header / trailer flags are dropped here
     // and the kernels see hdr_bits() == trl_bits() == 0
@@ -5836,6 +5852,13 @@ extern "C" int dmx_encode_async(dmx_ctx* c, const void* d_in, uint64_t n, void* 
     // DMX_F_BGZF: every member's CRC-32, one launch into the CRC scratch (a word per block:
     // nblk <= cap_blocks < crc_cap), which K4 reads
     const uint32_t* bcrc = NULL;
+    // DMX_F_FDICT: the DICTID, one launch over the dictionary into a word of the context; K4's first
+    // block reads it through the pointer that carries the members' CRC-32s under DMX_F_BGZF (the two
+    // flags exclude each other), an empty input's scan kernel through nfb
+    if (o.flags & DMX_F_FDICT) {
+        bcrc = c->nfb + 3;
+        if (dmx_dict_adler_launch(o.dict, dict_len, c->nfb + 3, s)) return -(int)E_DEVICE;
+    }
     if ((o.flags & DMX_F_BGZF) && nblk) {
         bcrc = c->crc_rem;
         dmx_crc32_blocks_launch(c, d_in, n, (uint32_t)o.sw, c->crc_rem, s);

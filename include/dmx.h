@@ -65,7 +65,9 @@ int deflate_compress(int fd_in, int fd_out, int fd_stats, swi sw, int ops);
  * Returns 0 or -E_*.  zlib decides what is a stream; a rejected one has this status, the same
  * from dmx_inflate_async's stream mode (tests/test_inflate_conformance.py):
  *   -E_ZHEAD    fewer than 2 bytes (or a gzip header cut short)
- *   -E_ZCMPMT / -E_ZSLWIN / -E_ZFCHCK / -E_ZPDICT   the zlib header: CM, CINFO, FCHECK, FDICT
+ *   -E_ZCMPMT / -E_ZSLWIN / -E_ZFCHCK / -E_ZPDICT   the zlib header: CM, CINFO, FCHECK, FDICT (here
+ *               always: this call has no dictionary to give; dmx_inflate_batch_dict_async and
+ *               dmx_inflate_dict_host take one, and there it means "none given, or another DICTID")
  *   -E_LEN      the input ends inside the DEFLATE data, whatever would have followed
  *   -E_ZBTYPE   BTYPE 3;   -E_ZNLEN  stored LEN != ~NLEN
  *   -E_ZINV     HLIT > 286, HDIST > 30, a 16 with no length before it, a repeat past
@@ -181,6 +183,19 @@ struct compress_stats {
                             data member, out_len includes the end-of-file member.  dmx_block_index:
                             bit = first bit of the member's DEFLATE data, 8 x (member offset + 18). */
 #define DMX_BGZF (DMX_F_BGZF | DMX_F_FINAL)
+#define DMX_F_FDICT 2048u /* container option: the zlib header names the dictionary of a DMX_F_DICT
+                            encode (RFC 1950 2.2) -- 78 BB and the DICTID, the Adler-32 of
+                            opts->dict[0, dict_len) most significant byte first, 6 bytes instead of 2,
+                            so that zlib.decompressobj(zdict=dict), inflateSetDictionary and
+                            dmx_inflate_batch_dict_async decode the stream.  The DICTID is computed
+                            on the device on the encode's stream.  Valid only with DMX_F_DICT and
+                            DMX_F_HEADER, without DMX_F_GZIP and DMX_F_BGZF, with opts->dict not NULL
+                            and 1 <= dict_len <= sw (the staged dictionary is then the whole
+                            dictionary, and the DICTID covers exactly the bytes the parse may
+                            reference); anything else is -E_INVAL.  The DEFLATE data is bit for bit
+                            that of the same encode without the flag; dmx_max_compressed_flags adds
+                            4.  dmx_encode_fd*, deflate_compress and dmx_encode_batch_async return
+                            -E_INVAL for it. */
 #define DMX_F_EXACT_SORT 16u  /* test hook: sort positions with the match-any grouping instead
                                 of lane-ordered LDS atomics (same result; used by the tests) */
 #define DMX_F_LAZY 8u    /* parse option: lazy evaluation, one position of
@@ -609,6 +624,58 @@ uint64_t dmx_inflate_batch_work(uint32_t nstreams);
 int dmx_inflate_batch_async(const void* d_z, uint64_t zbytes, const dmx_bstream* d_streams, uint32_t nstreams,
                             uint32_t flags, void* d_out, uint64_t out_bytes, dmx_bresult* d_results,
                             void* d_work, uint64_t work_bytes, dmx_batch_status* d_status, void* stream);
+/* The same batches with preset dictionaries (RFC 1950 2.2: FDICT and DICTID; zlib's
+ * inflateSetDictionary, Python's zdict=; DESIGN.md §3.1 "Dictionaries").  Everything
+ * dmx_inflate_batch_async promises holds: a status per stream, neighbours untouched, no byte read
+ * behind a stream, no allocation, no host synchronisation, a linear chain of launches that can be
+ * captured into a graph, DMX_BATCH_MEASURE.
+ * Dictionary j is d_dict[off, off + len) of d_dicts[j], of any length >= 0 at any alignment; stream k
+ * uses dictionary d_dict_of[k], or none where that is DMX_BATCH_NODICT.  d_dict_of == NULL: every
+ * stream uses dictionary 0 (none when ndicts == 0).  The last min(len, 32768) bytes prime the window;
+ * the DICTID is the Adler-32 of all len bytes, computed on the device by a kernel of the call, so the
+ * dictionaries may change between two replays of a captured call.  Only whole 16-byte aligned groups
+ * inside a dictionary and single bytes at its edges are loaded: no byte outside [off, off + len).
+ * Cost: every dictionary is folded by one workgroup of 256 threads, all len bytes of it (the DICTID
+ * covers them all), before the decode starts: 32 KiB is a few microseconds, but a dictionary of many
+ * megabytes is read by one CU and delays the whole batch -- pass only the bytes a writer passed to
+ * deflateSetDictionary, which keeps 32 KiB at most.
+ * zlib decides, as everywhere:
+ *   a zlib stream with FDICT: a 6-byte header.  With a dictionary whose Adler-32 is the stored DICTID
+ *     it decodes with the window primed; the Adler-32 trailer covers the output alone; in_used counts
+ *     the 6 bytes.  Without a dictionary, or with another DICTID: -E_ZPDICT.  A header that ends
+ *     inside the DICTID (2 to 5 bytes) is -E_ZHEAD, whether or not there is a dictionary.
+ *   a zlib stream without FDICT ignores its dictionary (zlib.decompressobj(zdict=d) on such a
+ *     stream): a distance before the first output byte stays -E_HUFDIS.
+ *   a raw stream with a dictionary: the window is always primed (inflateSetDictionary on a raw stream).
+ *   a gzip member has no dictionary and decodes as without one.
+ *   a distance greater than (output so far + primed bytes): -E_HUFDIS.
+ *   d_dict_of[k] >= ndicts and not DMX_BATCH_NODICT, or a d_dicts entry outside d_dict[0, dict_bytes):
+ *     that stream alone gets -E_RANGE (format 0 under AUTO), whatever its framing.
+ * Launches: reset, the dictionaries' Adler-32s (ndicts blocks of 256 threads; only when ndicts > 0),
+ * decode, and the CRC-32 pass as above.  d_work: 256-byte aligned, work_bytes >=
+ * dmx_inflate_batch_dict_work(nstreams, ndicts) -- a multiple of 256, monotone in both, equal to
+ * dmx_inflate_batch_work(nstreams) at ndicts == 0.
+ * Returns before any device call: what dmx_inflate_batch_async returns, and -E_INVAL for d_dicts NULL
+ * with ndicts > 0, d_dict NULL with dict_bytes > 0, d_dicts not 8-byte or d_dict_of not 4-byte aligned.
+ * dmx_inflate_batch_async itself is unchanged: its launches, its kernels, its statuses (an FDICT
+ * stream there is -E_ZPDICT). */
+typedef struct { uint64_t off, len; } dmx_bdict;   /* 16 bytes: dictionary j = d_dict[off, off + len) */
+#define DMX_BATCH_NODICT 0xFFFFFFFFu
+uint64_t dmx_inflate_batch_dict_work(uint32_t nstreams, uint32_t ndicts);
+int dmx_inflate_batch_dict_async(const void* d_z, uint64_t zbytes, const dmx_bstream* d_streams, uint32_t nstreams,
+                                 uint32_t flags,
+                                 const void* d_dict, uint64_t dict_bytes, const dmx_bdict* d_dicts, uint32_t ndicts,
+                                 const uint32_t* d_dict_of,      /* per stream: index or DMX_BATCH_NODICT; NULL = all use 0 */
+                                 void* d_out, uint64_t out_bytes, dmx_bresult* d_results,
+                                 void* d_work, uint64_t work_bytes, dmx_batch_status* d_status, void* stream);
+/* One stream of such a batch on the host (csrc/dmx_inflate.c), the host side of "host == GPU" for the
+ * statuses above: z[0, n) under fmt (DMX_BATCH_AUTO / ZLIB / GZIP / RAW) with the dictionary
+ * dict[0, dict_len) (dict == NULL: none; a non-NULL dict with dict_len 0 is an empty dictionary,
+ * DICTID 1).  *out is malloc'd (the caller frees it), *out_len the decoded bytes, *in_used (may be
+ * NULL) as in dmx_bresult.  Returns 0, -E_INVAL (out or out_len NULL, z NULL with n > 0, dict NULL
+ * with dict_len > 0, fmt above 3), -E_MALLOC, or the stream's status. */
+int dmx_inflate_dict_host(const void* z, uint64_t n, uint32_t fmt, const void* dict, uint64_t dict_len,
+                          void** out, uint64_t* out_len, uint64_t* in_used);
 /* Batches of independent buffers into independent streams (csrc/dmx_encode_batch.hip):
  * the encode's counterpart of dmx_inflate_batch_async.  nstreams buffers become nstreams complete
  * zlib streams, gzip members or raw DEFLATE streams, every one decodable on its own, in one chain of

@@ -40,6 +40,8 @@ def main():
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--loop-steps", type=int, default=2)
     ap.add_argument("--distinct-mib", type=int, default=64)
+    ap.add_argument("--inputs", default="", help="comma-separated input names (all three by default)")
+    ap.add_argument("--lib", default="", help="another libdmx.so to load, e.g. the parent commit's, for A/B runs")
     ap.add_argument("--label", default="")
     ap.add_argument("--out", default="", help="file to write the JSON line to (profiles/inflate_batch/<label>.json)")
     args = ap.parse_args()
@@ -49,6 +51,13 @@ def main():
 
     import deflate_compression_amd as D
 
+    if args.lib:   # an older library may lack newer entries: bind only what this tool calls, typed as the tree's
+        import ctypes
+        other, mine = ctypes.CDLL(os.path.abspath(args.lib)), D.lib()
+        for name in ("dmx_inflate_batch_work", "dmx_inflate_batch_async", "dmx_inflate_async", "dmx_gen_text"):
+            f, g = getattr(other, name), getattr(mine, name)
+            f.argtypes, f.restype = g.argtypes, g.restype
+        D._lib = other
     L = D.lib()
 
     def timed(fn, steps, warmup):
@@ -80,7 +89,10 @@ def main():
             comp[chunk] = [zlib.compress(tb[o:o + chunk], 6) for o in range(0, len(tb), chunk)]
         return comp[chunk]
 
+    only = [s for s in args.inputs.split(",") if s]
     for name, chunk, count in (("64k_x4096", 65536, 4096), ("1m_x1024", 1 << 20, 1024), ("1m_x64", 1 << 20, 64)):
+        if only and name not in only:
+            continue
         print(f"[{name}]", file=sys.stderr, flush=True)
         zs = streams_of(chunk)
         pick = [zs[k % len(zs)] for k in range(count)]
