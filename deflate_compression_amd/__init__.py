@@ -38,6 +38,7 @@ __all__ = [
     "DMX_BATCH_AUTO", "DMX_BATCH_ZLIB", "DMX_BATCH_GZIP", "DMX_BATCH_RAW", "DMX_BATCH_MEASURE",
     "inflate_batch_dict_async", "inflate_dict_host", "BDict", "DMX_BATCH_NODICT",
     "compress_batch", "compress_batch_async", "encode_batch_blocks", "EStream", "EResult", "EBatchStatus", "ERESULT_DTYPE",
+    "compress_batch_dict_async",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -229,6 +230,11 @@ def lib() -> ctypes.CDLL:
         "dmx_encode_batch_bound": ([u64, u32, i32, u32], u64),
         "dmx_ctx_reserve_batch": ([vp, u32, u32, i32, u32], ctypes.c_int),
         "dmx_encode_batch_async": ([vp, vp, u64, vp, u32, u32, ctypes.POINTER(Opts), vp, u64, vp, vp, vp], ctypes.c_int),
+        "dmx_encode_batch_dict_bound": ([u64, u32, i32, u32], u64),
+        "dmx_encode_batch_dict_geometry": ([u32p], None),
+        "dmx_ctx_reserve_batch_dict": ([vp, u32, u32, u32, i32, u32], ctypes.c_int),
+        "dmx_encode_batch_dict_async": ([vp, vp, u64, vp, u32, u32, vp, u64, vp, u32, vp, ctypes.POINTER(Opts), vp, u64, vp, vp,
+                                         vp], ctypes.c_int),
         "dmx_crc32_combine": ([u32, u32, u64], u32),
         "dmx_crc32_geometry": ([u32p, u32p], None),
         "dmx_fd_last_stats": ([ctypes.POINTER(FdStats)], ctypes.c_int),
@@ -906,8 +912,29 @@ def compress_batch_async(encoder, t_in, streams, nstreams: int, max_blocks: int,
                                             ctypes.c_void_p(s))
 
 
+def compress_batch_dict_async(encoder, t_in, streams, nstreams: int, max_blocks: int, dict_t, dicts, ndicts: int, dict_of,
+                              out, out_cap: int, results, status, opts: Opts | None = None, stream=None) -> int:
+    """dmx_encode_batch_dict_async on caller-owned CUDA tensors, as compress_batch_async (no
+    synchronisation: it can be captured into a graph): dict_t the dictionaries' bytes (uint8), dicts an
+    (ndicts, 2) int64 tensor of dmx_bdict records (off, len) into it, dict_of an int32 / uint32 tensor
+    with a dictionary index per stream (DMX_BATCH_NODICT, or -1 as int32: none) or None (every stream
+    uses dictionary 0).  opts.flags holds DMX_F_DICT.  The encoder must be reserved
+    (Encoder.reserve_batch_dict)."""
+    import torch
+    dev = out.device
+    o = opts or encoder.opts
+    with torch.cuda.device(dev):
+        s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        return lib().dmx_encode_batch_dict_async(encoder._ctx, _ptr(t_in), t_in.numel() if t_in is not None else 0,
+                                                 _ptr(streams), nstreams, max_blocks, _ptr(dict_t),
+                                                 dict_t.numel() if dict_t is not None else 0, _ptr(dicts), ndicts,
+                                                 _ptr(dict_of), ctypes.byref(o), ctypes.c_void_p(out.data_ptr()), out_cap,
+                                                 ctypes.c_void_p(results.data_ptr()), ctypes.c_void_p(status.data_ptr()),
+                                                 ctypes.c_void_p(s))
+
+
 def compress_batch(bufs, streams=None, fmt: str = "zlib", sw: int = 32768, max_chain: int = 0, lazy: bool = False,
-                   flags: int = 0, encoder=None, strict: bool = True):
+                   flags: int = 0, encoder=None, strict: bool = True, zdict=None, dict_of=None, fdict: bool = True):
     """Compress many independent buffers into as many independent zlib streams, gzip members or raw
     DEFLATE streams on the GPU, in one chain of launches (dmx_encode_batch_async): bufs is a list of
     bytes-like objects, packed into one device tensor here, or a contiguous uint8 CUDA tensor with
@@ -917,12 +944,23 @@ def compress_batch(bufs, streams=None, fmt: str = "zlib", sw: int = 32768, max_c
     streams packed back to back as a uint8 CUDA tensor, an int64 CUDA tensor of n + 1 with stream k at
     out[offsets[k]:offsets[k + 1]], and a numpy structured array of the EResult records (status,
     nblocks, out_off, out_len, check).  One synchronisation.  strict: a stream with a status, or a
-    status of the whole call, raises DeflateError (a stream's names the lowest such index)."""
+    status of the whole call, raises DeflateError (a stream's names the lowest such index).
+    zdict: preset dictionaries (dmx_encode_batch_dict_async) -- one bytes-like object or a list of them;
+    dict_of: the dictionary index of every stream, -1 or None for none (by default every stream uses
+    dictionary 0), as in inflate_batch.  Stream k is then what a single encode of buffer k against its
+    dictionary gives.  fmt is "zlib" or "raw"; fdict (zlib only): the streams that name a dictionary
+    carry FDICT and its DICTID, for zlib.decompressobj(zdict=) and inflate_batch(zdict=); fdict=False
+    writes 78 9C headers over the same history, which only a decoder that is given the dictionary by
+    other means can read.  Without zdict the call is dmx_encode_batch_async, exactly as before."""
     import numpy as np
     import torch
     L = lib()
     if fmt not in _EBATCH_FMT:
         raise ValueError("fmt is one of " + ", ".join(_EBATCH_FMT))
+    if zdict is None and dict_of is not None:
+        raise ValueError("dict_of comes with zdict")
+    if zdict is not None and fmt == "gzip":
+        raise ValueError("a gzip member has no preset dictionary: fmt is zlib or raw with zdict")
     if isinstance(bufs, torch.Tensor):
         if streams is None:
             raise ValueError("a tensor comes with streams, an (n, 2) int64 array of (off, len)")
@@ -940,12 +978,14 @@ def compress_batch(bufs, streams=None, fmt: str = "zlib", sw: int = 32768, max_c
     dev = tin.device
     n = sa.shape[0]
     o = Opts(sw, max_chain, _EBATCH_FMT[fmt] | flags | (DMX_F_LAZY if lazy else 0), 0)
+    if zdict is not None:
+        o.flags |= DMX_F_DICT | (DMX_F_FDICT if fdict and fmt == "zlib" else 0)
     # the lengths are known here: the exact block count (a stream outside the tensor has none)
     total = int(tin.numel())
     inside = [(0 <= off <= total and 0 <= ln <= total - off) for off, ln in sa.tolist()]
     good = [int(ln) for (off, ln), ok in zip(sa.tolist(), inside) if ok]
     nblk = encode_batch_blocks(good, sw)
-    cap = int(L.dmx_encode_batch_bound(sum(good), n, sw, o.flags))
+    cap = int((L.dmx_encode_batch_dict_bound if zdict is not None else L.dmx_encode_batch_bound)(sum(good), n, sw, o.flags))
     own = encoder is None
     enc = Encoder(dev.index or 0, 0, sw, max_chain, o.flags) if own else encoder
     # everything runs on one stream: the current one, or a stream of this call's where the current one
@@ -954,13 +994,21 @@ def compress_batch(bufs, streams=None, fmt: str = "zlib", sw: int = 32768, max_c
     work = cur if cur.cuda_stream else torch.cuda.Stream(dev)
     work.wait_stream(cur)
     try:
-        enc.reserve_batch(nblk, n, sw, o.flags)
+        if zdict is None:
+            enc.reserve_batch(nblk, n, sw, o.flags)
+        else:
+            dict_t, dicts_t, nd, of_t = _batch_dicts(zdict, None, dict_of, n, dev)
+            enc.reserve_batch_dict(nblk, n, nd, sw, o.flags)
         with torch.cuda.stream(work):
             dt = torch.from_numpy(np.ascontiguousarray(sa)).to(dev) if n else torch.zeros((1, 2), dtype=torch.int64, device=dev)
             out = torch.empty(cap, dtype=torch.uint8, device=dev)
             res = torch.zeros(max(n, 1) * 4, dtype=torch.int64, device=dev)
             st = torch.zeros(4, dtype=torch.int64, device=dev)
-            _check(compress_batch_async(enc, tin, dt, n, nblk, out, cap, res, st, o), "dmx_encode_batch_async")
+            if zdict is None:
+                _check(compress_batch_async(enc, tin, dt, n, nblk, out, cap, res, st, o), "dmx_encode_batch_async")
+            else:
+                _check(compress_batch_dict_async(enc, tin, dt, n, nblk, dict_t, dicts_t, nd, of_t, out, cap, res, st, o),
+                       "dmx_encode_batch_dict_async")
             offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)   # out_off of every record, then the total
             offsets[:n] = res.view(-1, 4)[:n, 1]
             offsets[n] = st[2]
@@ -1106,6 +1154,12 @@ class Encoder:
         streams (dmx_ctx_reserve_batch; synchronises only when it allocates)."""
         _check(self._L.dmx_ctx_reserve_batch(self._ctx, max_blocks, max_streams, sw, flags), "dmx_ctx_reserve_batch")
 
+    def reserve_batch_dict(self, max_blocks: int, max_streams: int, max_dicts: int, sw: int = 32768, flags: int = 0) -> None:
+        """Workspace, block table, plan scratch, chain slots for max_blocks + max_dicts and the DICTID
+        words of a dictionary batch (dmx_ctx_reserve_batch_dict; synchronises only when it allocates)."""
+        _check(self._L.dmx_ctx_reserve_batch_dict(self._ctx, max_blocks, max_streams, max_dicts, sw, flags),
+               "dmx_ctx_reserve_batch_dict")
+
     def encode_async(self, d_in: int, n: int, d_out: int, cap: int, stream: int | None = None,
                      opts: Opts | None = None) -> None:
         o = opts or self.opts
@@ -1232,12 +1286,12 @@ class Encoder:
 
     STAGES = ("pre", "match", "huff", "scan", "pack")
 
-    HOOKS = {"worklist": 1, "dedupe": 2, "scan3": 3}   # DMX_HOOK_* (include/dmx.h)
+    HOOKS = {"worklist": 1, "dedupe": 2, "scan3": 3, "bdict_simple": 4}   # DMX_HOOK_* (include/dmx.h)
     WORKLIST = {None: -1, "0": 0, "list": 1, "plain": 2}
 
     def set_hook(self, name: str, value) -> None:
         """Test hooks of this context (dmx_ctx_set_hook): "worklist" None (adaptive) / "0" /
-        "list" / "plain"; "dedupe" None / 0 / 1; "scan3" 0 / 1.  Every setting must give the
+        "list" / "plain"; "dedupe" None / 0 / 1; "scan3" 0 / 1; "bdict_simple" 0 / 1.  Every setting must give the
         same stream; they pick launch shapes only."""
         if name == "worklist":
             v = self.WORKLIST[value]

@@ -78,6 +78,10 @@ struct dmx_ctx {
     void* bplan;          // the plan's scratch for cap_bstreams streams: head, tile sums, block starts
     uint64_t cap_bstreams;
     int last_batch;       // the last encode was a batch (dmx_block_index: -E_INVAL)
+    // batch encodes against dictionaries (dmx_encode_batch_dict.hip; dmx_ctx_reserve_batch_dict only)
+    uint32_t* bdictid;    // cap_bdicts DICTIDs: the dictionaries' Adler-32s of the call in flight
+    uint64_t cap_bdicts;
+    uint64_t chain_dicts; // chain slots kept beyond a slot per block and the single encode's one
     // timing: a ring of event sets so timed encodes never block the host
     int timing;       // bit k: record event k (set_timing: 1 = all six, 0x100 | s = stage s's two)
     hipEvent_t ev[DMX_EV_RING][6];
@@ -90,6 +94,7 @@ struct dmx_ctx {
     int hk_wl;       // -1 adaptive launch shapes, 0 no work lists, 1 list shapes, 2 per-block shapes (DMX_WORKLIST)
     int hk_dedupe;   // -1 adaptive, 0 / 1 the uniform-block dedupe forced off / on (DMX_DEDUPE)
     int hk_scan3;    // 1: K3 in three launches at any size (DMX_SCAN3)
+    int hk_bdict_simple;   // 1: the dictionary batch's history search with a workgroup per table entry
 };
 
 #define DMX_HIDDEN __attribute__((visibility("hidden")))
@@ -110,6 +115,10 @@ DMX_HIDDEN int dmx_crc32_ranges_launch(const void* d_in, uint64_t n, const dmx_i
 // the Adler-32 of d_dict[0, n) into *d_adl, one launch (dmx_inflate_dev.hip: dmx_dict_adler_kernel's
 // arithmetic on one dictionary given by value): the DICTID of a DMX_F_FDICT encode
 DMX_HIDDEN int dmx_dict_adler_launch(const void* d_dict, uint64_t n, uint32_t* d_adl, hipStream_t s);
+// dmx_dict_adler_kernel over ndicts records: d_adl[j] = the Adler-32 of dictionary j, 0 for a record
+// outside d_dict[0, dict_bytes) (dmx_encode_batch_dict_async's DICTIDs)
+DMX_HIDDEN int dmx_dict_adler_batch_launch(const void* d_dict, uint64_t dict_bytes, const dmx_bdict* d_dicts,
+                                           uint32_t ndicts, uint32_t* d_adl, hipStream_t s);
 // the CRC-32 pass of dmx_inflate_batch_async (dmx_crc.hip): every stream with status 0 and format
 // gzip is finished -- -E_CRC, else the decode's note of a wrong ISIZE as -E_LEN -- and counted in
 // the summary

@@ -185,4 +185,86 @@ DMX_EB_HD static inline uint32_t dmx_eb_blocks_bound(uint64_t total_in, uint32_t
     return b > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)b;
 }
 
+// ---- dmx_encode_batch_dict_async: the same plan where a stream's verdict also depends on its preset
+// dictionary.  The functions above keep their signatures (the host twin of the plain batch runs
+// them); these sit beside them and the kernels of the dictionary batch call these instead.
+struct dmx_ebd {
+    const dmx_bdict* dicts;    // ndicts records into d_dict[0, dict_bytes)
+    const uint32_t* dict_of;   // per stream: an index or DMX_BATCH_NODICT; NULL: every stream uses 0
+    uint64_t dict_bytes;
+    uint32_t ndicts;
+    uint32_t fdict;            // DMX_F_FDICT: the header names the dictionary, which is then whole
+};
+// the dictionary stream k names: an index, or DMX_BATCH_NODICT (also every stream of a call without
+// dictionaries and without d_dict_of) -- dmx_inflate_batch_dict_async's rule
+DMX_EB_HD static inline uint32_t dmx_ebd_index(const dmx_ebd& d, uint32_t k) {
+    return d.dict_of ? d.dict_of[k] : d.ndicts ? 0u : DMX_BATCH_NODICT;
+}
+// record j lies inside d_dict[0, dict_bytes): the test that cannot wrap
+DMX_EB_HD static inline bool dmx_ebd_inside(const dmx_bdict& r, uint64_t dict_bytes) {
+    return r.off <= dict_bytes && r.len <= dict_bytes - r.off;
+}
+// stream k's status: -E_RANGE for a buffer outside d_in, a dictionary index at or above ndicts or a
+// record outside d_dict; under DMX_F_FDICT -E_INVAL for a dictionary of length 0 or above sw, the
+// single encode's verdict (its DICTID must cover what the parse may reference); else 0
+DMX_EB_HD static inline int32_t dmx_ebd_status(const dmx_estream* st, uint32_t k, uint64_t in_bytes, uint32_t sw,
+                                               const dmx_ebd& d) {
+    if (!dmx_eb_valid(st[k], in_bytes)) return -(int32_t)E_RANGE;
+    const uint32_t di = dmx_ebd_index(d, k);
+    if (di == DMX_BATCH_NODICT) return 0;
+    if (di >= d.ndicts || !dmx_ebd_inside(d.dicts[di], d.dict_bytes)) return -(int32_t)E_RANGE;
+    if (d.fdict && (d.dicts[di].len < 1 || d.dicts[di].len > sw)) return -(int32_t)E_INVAL;
+    return 0;
+}
+// the history of a first block: the last min(len, sw) bytes of the stream's dictionary (hn 0: none),
+// at d_dict + *off, its chain slot *slot = the dictionary's index.  For a stream with status 0.
+DMX_EB_HD static inline uint32_t dmx_ebd_history(const dmx_ebd& d, uint32_t k, uint32_t sw, uint64_t* off, uint32_t* slot) {
+    const uint32_t di = dmx_ebd_index(d, k);
+    *off = 0;
+    *slot = 0;
+    if (di == DMX_BATCH_NODICT) return 0;
+    const dmx_bdict r = d.dicts[di];
+    const uint32_t hn = r.len < sw ? (uint32_t)r.len : sw;
+    *off = r.off + (r.len - hn);
+    *slot = di;
+    return hn;
+}
+DMX_EB_HD static inline uint64_t dmx_ebd_count(const dmx_estream* st, uint32_t k, uint64_t in_bytes, uint32_t sw,
+                                               const dmx_ebd& d) {
+    return dmx_ebd_status(st, k, in_bytes, sw, d) ? 0u : dmx_eb_count(st[k], in_bytes, sw);
+}
+// dmx_eb_stream_sums, dmx_eb_start and dmx_eb_entry with the dictionary's verdict
+DMX_EB_HD static inline dmx_eb_tile dmx_ebd_stream_sums(const dmx_estream* st, uint32_t k, uint64_t in_bytes, uint32_t sw,
+                                                        const dmx_ebd& d) {
+    dmx_eb_tile t;
+    const bool ok = dmx_ebd_status(st, k, in_bytes, sw, d) == 0;
+    t.blocks = ok ? dmx_eb_count(st[k], in_bytes, sw) : 0u;
+    t.bytes = ok ? st[k].in_len : 0u;
+    t.nfailed = ok ? 0u : 1u;
+    t.first_bad = ok ? DMX_EB_NOBAD : k;
+    return t;
+}
+DMX_EB_HD static inline void dmx_ebd_start(const dmx_estream* st, uint32_t k, uint32_t nstreams, uint64_t in_bytes,
+                                           uint32_t sw, const dmx_ebd& d, uint64_t before, uint64_t* starts,
+                                           dmx_eresult* res) {
+    const uint64_t c = dmx_ebd_count(st, k, in_bytes, sw, d);
+    starts[k] = before;
+    if (k + 1 == nstreams) starts[nstreams] = dmx_eb_sat(before, c);
+    dmx_eresult r;
+    r.status = dmx_ebd_status(st, k, in_bytes, sw, d);
+    r.nblocks = c > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)c;
+    r.out_off = 0;
+    r.out_len = 0;
+    r.check = 0;
+    r.reserved = 0;
+    res[k] = r;
+}
+// (starts[] already holds the dictionary's verdict: a refused stream has no blocks, so no entry finds it)
+DMX_EB_HD static inline dmx_bblk dmx_ebd_entry(const dmx_estream* st, const uint64_t* starts, uint32_t nstreams,
+                                               const dmx_eb_head* head, uint32_t sw, const dmx_ebd& d, uint32_t b) {
+    dmx_bblk e = dmx_eb_entry(st, starts, nstreams, head, sw, b);
+    if (!(e.len & DMX_BB_VOID) && dmx_ebd_index(d, e.stream) != DMX_BATCH_NODICT) e.len |= DMX_BB_DICT;
+    return e;
+}
+
 #endif

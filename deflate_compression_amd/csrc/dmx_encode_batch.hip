@@ -178,16 +178,24 @@ __device__ __forceinline__ Mono eb_own(const dmx_blkinfo& bi) {
 }
 // and with the framing of its stream: x -> align8(x) + header bits in front of a first block,
 // x -> align8(x) + trailer bits behind a last one
+// DB (dmx_encode_batch_dict_async): the header's width is the stream's own -- under DMX_F_FDICT 48
+// bits where it names a dictionary (DMX_BB_DICT), 16 where it has none; 48 = 16 mod 32
+template <bool DB>
+__device__ __forceinline__ uint32_t eb_hdr(uint32_t marks, uint32_t flags) {
+    if constexpr (DB) return (marks & DMX_BB_DICT) ? hdr_bits(flags) : hdr_bits(flags & ~DMX_F_FDICT);
+    else return hdr_bits(flags);
+}
+template <bool DB = false>
 __device__ __forceinline__ Mono eb_elem(const dmx_blkinfo& bi, uint32_t marks, uint32_t flags) {
     Mono e = eb_own(bi);
-    if (marks & DMX_BB_FIRST) { const Mono h = {1, 0, hdr_bits(flags)}; e = mcompose(h, e); }
+    if (marks & DMX_BB_FIRST) { const Mono h = {1, 0, eb_hdr<DB>(marks, flags)}; e = mcompose(h, e); }
     if (marks & DMX_BB_LAST) { const Mono t = {1, 0, trl_bits(flags)}; e = mcompose(e, t); }
     return e;
 }
 
-__global__ __launch_bounds__(SCAN_TILE) void dmx_eb_scan_tile_kernel(dmx_blkinfo* __restrict__ info,
-                                                                    const dmx_bblk* __restrict__ tab, uint32_t max_blocks,
-                                                                    uint32_t flags, ScanTile* __restrict__ tiles) {
+template <bool DB>
+__device__ __forceinline__ void eb_scan_tile(dmx_blkinfo* __restrict__ info, const dmx_bblk* __restrict__ tab,
+                                             uint32_t max_blocks, uint32_t flags, ScanTile* __restrict__ tiles) {
     __shared__ Mono wtot[SCAN_TILE / 64];
     __shared__ uint64_t red[SCAN_TILE / 64][4];
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -198,7 +206,7 @@ __global__ __launch_bounds__(SCAN_TILE) void dmx_eb_scan_tile_kernel(dmx_blkinfo
     const bool real = !(marks & DMX_BB_VOID);
     if (real) {
         const dmx_blkinfo bi = info[b];
-        e = eb_elem(bi, marks, flags);
+        e = eb_elem<DB>(bi, marks, flags);
         nt = bi.ntok;
         ns = bi.btype == 0;
         nf = bi.btype == 1;
@@ -232,6 +240,11 @@ __global__ __launch_bounds__(SCAN_TILE) void dmx_eb_scan_tile_kernel(dmx_blkinfo
         T.adl_s1 = 0; T.adl_s2 = 0; T.ntok = t0; T.nsto = t1; T.nfix = t2;
         T.kinds = t3;   // (ScanSums::k0: the tile's real blocks, at most SCAN_TILE)
     }
+}
+__global__ __launch_bounds__(SCAN_TILE) void dmx_eb_scan_tile_kernel(dmx_blkinfo* __restrict__ info,
+                                                                    const dmx_bblk* __restrict__ tab, uint32_t max_blocks,
+                                                                    uint32_t flags, ScanTile* __restrict__ tiles) {
+    eb_scan_tile<false>(info, tab, max_blocks, flags, tiles);
 }
 
 // Where the batch ends: every stream ends on a byte boundary, so the composed layout applied to
@@ -281,6 +294,7 @@ __device__ __forceinline__ void eb_publish(dmx_result* __restrict__ res, uint32_
 // every word it shares -- with a neighbour, or with its stream's header and trailer, which the
 // finish kernel ORs in -- is zeroed for K4's ORs.  `write` false (-E_SZ for out_cap): the places
 // only, which the finish kernel reports; no byte of the output is touched.
+template <bool DB = false>
 __device__ __forceinline__ void eb_apply_block(dmx_blkinfo* __restrict__ info, const dmx_bblk* __restrict__ tab, uint32_t b,
                                                uint32_t flags, const Mono& tp, uint32_t* __restrict__ out32, bool write) {
     const uint32_t marks = tab[b].len;
@@ -290,7 +304,7 @@ __device__ __forceinline__ void eb_apply_block(dmx_blkinfo* __restrict__ info, c
     lp.c = bi.off_bits; lp.s = (uint32_t)(bi.len_bits >> 32); lp.a = bi.len_bits & 0xFFFFFFFFu;
     const uint64_t x = mapply(mcompose(tp, lp), 0);   // the end of the block before
     const uint64_t hs = align8(x);                    // a first block: its stream begins here
-    const uint64_t o = (marks & DMX_BB_FIRST) ? hs + hdr_bits(flags) : x;
+    const uint64_t o = (marks & DMX_BB_FIRST) ? hs + eb_hdr<DB>(marks, flags) : x;
     const uint64_t l = mapply(eb_own(bi), o) - o;
     info[b].off_bits = o;
     info[b].len_bits = l;
@@ -507,21 +521,32 @@ __global__ __launch_bounds__(CRC_T) void dmx_eb_crc_kernel(const uint8_t* __rest
 // bytes behind the block in its stream, not in the batch.  Then the stream's place (out_off,
 // out_len, from its first and last block's places), its check value, and -- unless the call is
 // -E_SZ -- its header and trailer ORed into the words eb_apply_block zeroed.
+// DB (dmx_encode_batch_dict_async): a stream's verdict and header come from its dictionary (d) -- under
+// DMX_F_FDICT 78 BB and the DICTID dictid[index] where it names one, 78 9C where it has none.
 #define EB_FIN_WAVES 4
-__global__ __launch_bounds__(64 * EB_FIN_WAVES) void dmx_eb_finish_kernel(const dmx_estream* __restrict__ st,
-                                                                          const uint64_t* __restrict__ starts,
-                                                                          uint32_t nstreams, uint64_t in_bytes, uint32_t sw,
-                                                                          uint32_t flags, const dmx_blkinfo* __restrict__ info,
-                                                                          const dmx_eb_head* __restrict__ head,
-                                                                          const dmx_result* __restrict__ res,
-                                                                          uint32_t* __restrict__ out32,
-                                                                          dmx_eresult* __restrict__ results) {
+template <bool DB>
+__device__ __forceinline__ void eb_finish(const dmx_estream* __restrict__ st, const uint64_t* __restrict__ starts,
+                                          uint32_t nstreams, uint64_t in_bytes, uint32_t sw, const uint32_t flags0,
+                                          const dmx_blkinfo* __restrict__ info, const dmx_eb_head* __restrict__ head,
+                                          const dmx_result* __restrict__ res, uint32_t* __restrict__ out32,
+                                          dmx_eresult* __restrict__ results, const dmx_ebd* d = nullptr,
+                                          const uint32_t* __restrict__ dictid = nullptr,
+                                          const dmx_bblk* __restrict__ tab = nullptr) {
+    uint32_t flags = flags0;
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t k = (uint64_t)blockIdx.x * EB_FIN_WAVES + (threadIdx.x >> 6);
     if (k >= nstreams) return;
     if (head->status) return;   // more blocks than max_blocks: nothing was laid out (the records hold zeros)
     const dmx_estream s = st[k];
-    const bool ok = dmx_eb_valid(s, in_bytes);
+    bool ok;
+    uint32_t di = DMX_BATCH_NODICT;   // DB: the dictionary the stream's header names
+    if constexpr (DB) {
+        ok = dmx_ebd_status(st, (uint32_t)k, in_bytes, sw, *d) == 0;
+        if (ok && (flags & DMX_F_FDICT)) di = dmx_ebd_index(*d, (uint32_t)k);
+        if (di == DMX_BATCH_NODICT) flags &= ~DMX_F_FDICT;
+    } else {
+        ok = dmx_eb_valid(s, in_bytes);
+    }
     const uint64_t b0 = starts[k], nb = ok ? starts[k + 1] - b0 : 0u;
     const uint64_t H = hdr_bits(flags), Tr = trl_bits(flags);
     uint64_t s1 = 0, s2 = 0;
@@ -541,7 +566,11 @@ __global__ __launch_bounds__(64 * EB_FIN_WAVES) void dmx_eb_finish_kernel(const 
         e0 = align8(last.off_bits + last.len_bits);
         end = e0 + Tr;
     } else {   // -E_RANGE: no bytes, where the next stream begins
-        o0 = b0 < head->nblocks ? info[b0].off_bits - H : res->end_bits;
+        if constexpr (DB) {   // (block b0 is the next stream's first: that header has its own width)
+            o0 = b0 < head->nblocks ? info[b0].off_bits - eb_hdr<true>(tab[b0].len, flags0) : res->end_bits;
+        } else {
+            o0 = b0 < head->nblocks ? info[b0].off_bits - H : res->end_bits;
+        }
         e0 = end = o0;
     }
     const uint32_t adler = (uint32_t)((((s.in_len % ADL_MOD + s2) % ADL_MOD) << 16) | ((1 + s1) % ADL_MOD));
@@ -554,6 +583,10 @@ __global__ __launch_bounds__(64 * EB_FIN_WAVES) void dmx_eb_finish_kernel(const 
         if (flags & DMX_F_GZIP) {   // 1F 8B 08 00, mtime 0, XFL 0, OS 255 (put_header's bytes, at any byte offset)
             gor_bits(out32, o0, 0x00088B1Fu, 32);
             gor_bits(out32, o0 + 64, 0xFF00u, 16);
+        } else if (DB && (flags & DMX_F_FDICT)) {   // 78 BB, the DICTID most significant byte first (put_header's bytes)
+            const uint32_t id = dictid[di];
+            gor_bits(out32, o0, 0xBB78u | ((id >> 24) << 16) | (((id >> 16) & 0xFFu) << 24), 32);
+            gor_bits(out32, o0 + 32, ((id >> 8) & 0xFFu) | ((id & 0xFFu) << 8), 16);
         } else {
             gor_bits(out32, o0, 0x9C78u, 16);
         }
@@ -565,6 +598,16 @@ __global__ __launch_bounds__(64 * EB_FIN_WAVES) void dmx_eb_finish_kernel(const 
         const uint32_t be = (check >> 24) | ((check >> 8) & 0xFF00u) | ((check << 8) & 0xFF0000u) | (check << 24);
         gor_bits(out32, e0, be, 32);
     }
+}
+__global__ __launch_bounds__(64 * EB_FIN_WAVES) void dmx_eb_finish_kernel(const dmx_estream* __restrict__ st,
+                                                                          const uint64_t* __restrict__ starts,
+                                                                          uint32_t nstreams, uint64_t in_bytes, uint32_t sw,
+                                                                          uint32_t flags, const dmx_blkinfo* __restrict__ info,
+                                                                          const dmx_eb_head* __restrict__ head,
+                                                                          const dmx_result* __restrict__ res,
+                                                                          uint32_t* __restrict__ out32,
+                                                                          dmx_eresult* __restrict__ results) {
+    eb_finish<false>(st, starts, nstreams, in_bytes, sw, flags, info, head, res, out32, results);
 }
 
 // ---- host ----

@@ -1075,6 +1075,11 @@ int dmx_dict_adler_launch(const void* d_dict, uint64_t n, uint32_t* d_adl, hipSt
     hipLaunchKernelGGL(dmx_dict_adler_one_kernel, dim3(1), dim3(256), 0, s, (const uint8_t*)d_dict, n, d_adl);
     return hipGetLastError() == hipSuccess ? 0 : -(int)E_DEVICE;
 }
+int dmx_dict_adler_batch_launch(const void* d_dict, uint64_t dict_bytes, const dmx_bdict* d_dicts, uint32_t ndicts,
+                                uint32_t* d_adl, hipStream_t s) {
+    hipLaunchKernelGGL(dmx_dict_adler_kernel, dim3(ndicts), dim3(256), 0, s, (const uint8_t*)d_dict, dict_bytes, d_dicts, d_adl);
+    return hipGetLastError() == hipSuccess ? 0 : -(int)E_DEVICE;
+}
 
 template <bool MEASURE, bool DICT = false>
 __global__ __launch_bounds__(64) void dmx_inflate_batch_kernel(const uint8_t* __restrict__ z, uint64_t zbytes,

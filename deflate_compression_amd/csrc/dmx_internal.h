@@ -45,10 +45,12 @@ typedef struct {
     uint64_t off;       /* input offset of the block's first byte in d_in */
     uint32_t len;       /* DMX_BB_LEN: its bytes, 0..sw (0: the one block of an empty stream), with
                          * DMX_BB_FIRST / DMX_BB_LAST for the first / last block of its stream; or
-                         * DMX_BB_VOID: no block (an entry beyond the batch's real block count) */
+                         * DMX_BB_VOID: no block (an entry beyond the batch's real block count); DMX_BB_DICT
+                         * (dmx_encode_batch_dict_async only): its stream names a preset dictionary */
     uint32_t stream;    /* index of its stream */
 } dmx_bblk;
 #define DMX_BB_LEN 0xFFFFu
+#define DMX_BB_DICT 0x10000u
 #define DMX_BB_VOID 0x20000000u
 #define DMX_BB_FIRST 0x40000000u
 #define DMX_BB_LAST 0x80000000u

@@ -5501,15 +5501,17 @@ static int ctx_reserve_scratch(dmx_ctx* c) {
         HIPCHK(dmx_malloc(&c->split, cb * sizeof(SplitScratch)));
         c->cap_split = cb;
     }
-    if ((c->want & DMX_F_DICT) && c->cap_chain < cb + 1) {
+    // (chain_dicts: the dictionaries of a batch, dmx_ctx_reserve_batch_dict; 0 otherwise)
+    const uint64_t slots = cb + 1 + c->chain_dicts;
+    if ((c->want & DMX_F_DICT) && c->cap_chain < slots) {
         if (c->chs) (void)hipFree(c->chs);
         if (c->che) (void)hipFree(c->che);
         c->chs = NULL;
         c->che = NULL;
         c->cap_chain = 0;
-        HIPCHK(dmx_malloc(&c->chs, (cb + 1) * DMX_BLK * sizeof(uint16_t)));
-        HIPCHK(dmx_malloc(&c->che, (cb + 1) * DMX_NBUCKET * sizeof(uint16_t)));
-        c->cap_chain = cb + 1;
+        HIPCHK(dmx_malloc(&c->chs, slots * DMX_BLK * sizeof(uint16_t)));
+        HIPCHK(dmx_malloc(&c->che, slots * DMX_NBUCKET * sizeof(uint16_t)));
+        c->cap_chain = slots;
     }
     if (getenv("DMX_STAMPS") && c->dbg_cap < cb) {
         if (c->dbg) (void)hipFree(c->dbg);
@@ -5645,6 +5647,7 @@ extern "C" void dmx_ctx_destroy(dmx_ctx* c) {
     if (c->split) (void)hipFree(c->split);
     if (c->btab) (void)hipFree(c->btab);
     if (c->bplan) (void)hipFree(c->bplan);
+    if (c->bdictid) (void)hipFree(c->bdictid);
     for (int j = 0; j < DMX_EV_RING; j++)
         for (int k = 0; k < 6; k++) if (c->ev[j][k]) (void)hipEventDestroy(c->ev[j][k]);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -5709,6 +5712,10 @@ extern "C" int dmx_ctx_set_hook(dmx_ctx* c, int hook, int value) {
         case DMX_HOOK_SCAN3:
             if (value < 0 || value > 1) return -(int)E_RANGE;
             c->hk_scan3 = value;
+            return 0;
+        case DMX_HOOK_BDICT_SIMPLE:
+            if (value < 0 || value > 1) return -(int)E_RANGE;
+            c->hk_bdict_simple = value;
             return 0;
         default:
             return -(int)E_INVAL;
@@ -6032,3 +6039,5 @@ extern "C" int dmx_last_subblock(dmx_ctx* c, uint32_t blk, uint32_t sub, uint32_
 // batch instantiations of K0 / K1 / K4, K3's batch layout and the per-stream finish have a file of
 // their own, compiled into this translation unit as dmx_crc.hip is.
 #include "dmx_encode_batch.hip"
+// ... and against preset dictionaries (dmx_encode_batch_dict_async)
+#include "dmx_encode_batch_dict.hip"

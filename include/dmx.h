@@ -344,11 +344,14 @@ int dmx_fault_set(const char* spec);
  * created (DMX_WORKLIST = 0 | list | plain, DMX_DEDUPE = 0 | 1, DMX_SCAN3 = 1); an encode
  * never reads the environment.  Values: DMX_HOOK_WORKLIST -1 adaptive (default), 0 no work
  * lists, 1 the list shapes, 2 a workgroup per block; DMX_HOOK_DEDUPE -1 adaptive, 0 off,
- * 1 on; DMX_HOOK_SCAN3 0 / 1 (K3 in three launches at any size).  Set them between encodes
+ * 1 on; DMX_HOOK_SCAN3 0 / 1 (K3 in three launches at any size); DMX_HOOK_BDICT_SIMPLE 0 / 1
+ * (dmx_encode_batch_dict_async's history search with a workgroup per table entry; no
+ * environment variable).  Set them between encodes
  * on the context's own thread.  Returns 0, -E_INVAL (unknown hook) or -E_RANGE. */
 #define DMX_HOOK_WORKLIST 1
 #define DMX_HOOK_DEDUPE 2
 #define DMX_HOOK_SCAN3 3
+#define DMX_HOOK_BDICT_SIMPLE 4
 int dmx_ctx_set_hook(dmx_ctx* ctx, int hook, int value);
 
 /* ---- GPU inflate, csrc/dmx_inflate_dev.hip ---- */
@@ -743,6 +746,59 @@ int dmx_encode_batch_async(dmx_ctx* ctx, const void* d_in, uint64_t in_bytes,
                            const dmx_estream* d_streams, uint32_t nstreams, uint32_t max_blocks,
                            const dmx_opts* opts, void* d_out, uint64_t out_cap,
                            dmx_eresult* d_results, dmx_ebatch_status* d_status, void* stream);
+/* Batches against preset dictionaries (csrc/dmx_encode_batch_dict.hip): the encode's
+ * counterpart of dmx_inflate_batch_dict_async, beside dmx_encode_batch_async as that call is beside
+ * dmx_inflate_batch_async.  The dictionaries are described as there: dictionary j is
+ * d_dict[d_dicts[j].off, + d_dicts[j].len), any length and alignment, device memory; stream k uses
+ * dictionary d_dict_of[k], or none where that is DMX_BATCH_NODICT; d_dict_of == NULL: every stream
+ * uses dictionary 0 (none when ndicts == 0).
+ * The bytes of stream k are exactly what dmx_encode_async writes for buffer k alone with the same opts
+ * and opts->dict / dict_len set to stream k's dictionary (opts->dict itself is ignored here); a stream
+ * without a dictionary is written as with DMX_F_FDICT cleared, a 78 9C header and no history for its
+ * first block.  So block 0 of a stream searches the last min(len, sw) bytes of its dictionary, block
+ * j >= 1 searches block j - 1 of its own stream, and no block searches another stream's bytes.
+ * Every dictionary is sorted once per call, however many streams share it.  Under DMX_F_FDICT a
+ * stream that names a dictionary begins 78 BB and the DICTID, the dictionary's Adler-32, which a
+ * kernel of the call computes: the dictionaries' bytes may change between two replays of a captured
+ * call.
+ * opts->flags must hold DMX_F_DICT, and frame DMX_ZLIB or DMX_F_FINAL alone (raw); DMX_F_FDICT only
+ * with DMX_ZLIB.  DMX_F_GZIP, DMX_F_BGZF, DMX_F_SPLIT, half a container or a missing DMX_F_DICT
+ * return -E_INVAL.  The parse and block options work as in a single encode.
+ * Everything dmx_encode_batch_async promises holds: streams packed in index order, a status per
+ * stream, neighbours untouched, the -E_SZ two-call idiom for max_blocks and out_cap, no allocation,
+ * no host synchronisation, a linear chain of launches whose number and grids follow from nstreams,
+ * max_blocks, ndicts, opts and the device's size, capturable into a graph; every record is reset by
+ * a kernel; dmx_encode_result gives the totals; dmx_block_index is -E_INVAL.
+ * Per stream (no blocks, out_len 0, neighbours keep their bytes): -E_RANGE for a buffer outside
+ * d_in, for d_dict_of[k] >= ndicts that is not DMX_BATCH_NODICT, and for a d_dicts record outside
+ * d_dict[0, dict_bytes) (a test that cannot wrap); under DMX_F_FDICT -E_INVAL for a dictionary of
+ * length 0 or above sw, the single encode's verdict.  Without DMX_F_FDICT a dictionary of length 0
+ * is no history and a longer one gives its last sw bytes.  nfailed counts both, first_bad is the
+ * lowest such index.
+ * The context must be reserved with dmx_ctx_reserve_batch_dict(ctx, max_blocks, max_streams,
+ * max_dicts, sw, flags), the only place that allocates: what dmx_ctx_reserve_batch allocates, chain
+ * slots for max_blocks + max_dicts (a slot is 64 KiB of sorted positions and 16 KiB of bucket ends
+ * whatever sw is: 80 KiB per block beside the workspace's own 260 KiB per block, about 5 GB of
+ * slots for 65 536 one-block streams), and max_dicts DICTID words.  On a context not reserved for it
+ * the call returns -E_SZ.  dmx_encode_batch_dict_bound: dmx_encode_batch_bound with 4 more bytes per
+ * stream under DMX_F_FDICT.  dmx_encode_batch_dict_geometry (tests): the workgroups of the history
+ * search's loop, one per compute unit of the current device; a call launches at most that many and
+ * at most max_blocks, each over a contiguous range of table entries.  DMX_HOOK_BDICT_SIMPLE 1 (tests,
+ * measurements) runs that search with a workgroup per table entry instead, as the single encode
+ * does; the output is the same.
+ * Returns before any device call: -E_INVAL (as dmx_encode_batch_async; d_dicts NULL with ndicts > 0,
+ * d_dict NULL with dict_bytes > 0, d_dicts not 8-byte or d_dict_of not 4-byte aligned; the flags
+ * above), -E_RANGE (as there; ndicts above 0x7FFFFFFF), -E_SZ (the reservation); else 0 or -E_DEVICE. */
+uint64_t dmx_encode_batch_dict_bound(uint64_t total_in, uint32_t nstreams, int32_t sw, uint32_t flags);
+void dmx_encode_batch_dict_geometry(uint32_t* hist_grid);
+int dmx_ctx_reserve_batch_dict(dmx_ctx* ctx, uint32_t max_blocks, uint32_t max_streams, uint32_t max_dicts,
+                               int32_t sw, uint32_t flags);
+int dmx_encode_batch_dict_async(dmx_ctx* ctx, const void* d_in, uint64_t in_bytes,
+                                const dmx_estream* d_streams, uint32_t nstreams, uint32_t max_blocks,
+                                const void* d_dict, uint64_t dict_bytes, const dmx_bdict* d_dicts, uint32_t ndicts,
+                                const uint32_t* d_dict_of,   /* per stream: index or DMX_BATCH_NODICT; NULL = all use 0 */
+                                const dmx_opts* opts, void* d_out, uint64_t out_cap,
+                                dmx_eresult* d_results, dmx_ebatch_status* d_status, void* stream);
 /* Host-buffer convenience (H2D, index, decode, D2H) on the cached per-device context
  * dmx_encode_host uses: any BGZF file z[0..zlen) into out. *out_len receives the decoded length
  * (the sum of the ISIZEs) whenever the file indexes, also when out_cap is too small (-E_SZ,
