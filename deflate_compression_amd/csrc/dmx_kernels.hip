@@ -33,6 +33,7 @@
 #include <string.h>
 
 #include "dmx_internal.h"
+#include "dmx_extbits.h"
 #include "../../include/dmx.h"
 
 #define MAXLEN 258
@@ -283,7 +284,8 @@ __device__ __forceinline__ uint32_t wshr(uint32_t v, uint32_t lane0) {   // lane
 // Length of a candidate known to match bytes [0, kk): 24 bytes in the first LDS round trip
 // (most extensions end there), then 32 per round trip.
 // Each side is read as 9 aligned words and realigned with v_alignbyte (one VALU per 4
-// bytes); the first differing word comes from a mask of non-zero xors.
+// bytes); the first differing bit is the min over the words of v_ffbl(xor) + 32 t, saturating
+// (dmx_first_diff_bit, the idiom of the register compares): ~0 = all equal.
 #ifndef EXT_W2
 #define EXT_W2 8   // words compared in each later round (reads reach 4 EXT_W2 + 4 bytes past kk)
 #endif
@@ -297,19 +299,12 @@ __device__ __forceinline__ uint32_t ext_len2(const uint32_t* A, uint32_t i, cons
         uint32_t wa[EXT_W1 + 1], wc[EXT_W1 + 1];
 #pragma unroll
         for (int t = 0; t < EXT_W1 + 1; t++) { wa[t] = A[a + t]; wc[t] = B[c + t]; }
-        uint32_t x[EXT_W1], nz = 0;
+        uint32_t x[EXT_W1];
 #pragma unroll
-        for (int t = 0; t < EXT_W1; t++) {
+        for (int t = 0; t < EXT_W1; t++)
             x[t] = __builtin_amdgcn_alignbyte(wa[t + 1], wa[t], sa) ^ __builtin_amdgcn_alignbyte(wc[t + 1], wc[t], sc);
-            nz |= (x[t] != 0 ? 1u : 0u) << t;
-        }
-        if (nz) {
-            const uint32_t t0 = (uint32_t)__builtin_ctz(nz);
-            uint32_t xv = x[0];
-#pragma unroll
-            for (int t = 1; t < EXT_W1; t++) xv = (t0 == (uint32_t)t) ? x[t] : xv;
-            return kk + 4 * t0 + ((uint32_t)__builtin_ctz(xv) >> 3);
-        }
+        const uint32_t m = dmx_first_diff_bit<EXT_W1>(x);
+        if (m != 0xFFFFFFFFu) return kk + (m >> 3);
         kk += 4 * EXT_W1;
         if (kk >= lim) return kk;
     }
@@ -318,19 +313,12 @@ __device__ __forceinline__ uint32_t ext_len2(const uint32_t* A, uint32_t i, cons
         uint32_t wa[EXT_W2 + 1], wc[EXT_W2 + 1];
 #pragma unroll
         for (int t = 0; t < EXT_W2 + 1; t++) { wa[t] = A[a + t]; wc[t] = B[c + t]; }
-        uint32_t x[EXT_W2], nz = 0;
+        uint32_t x[EXT_W2];
 #pragma unroll
-        for (int t = 0; t < EXT_W2; t++) {
+        for (int t = 0; t < EXT_W2; t++)
             x[t] = __builtin_amdgcn_alignbyte(wa[t + 1], wa[t], sa) ^ __builtin_amdgcn_alignbyte(wc[t + 1], wc[t], sc);
-            nz |= (x[t] != 0 ? 1u : 0u) << t;
-        }
-        if (nz) {
-            const uint32_t t0 = (uint32_t)__builtin_ctz(nz);
-            uint32_t xv = x[0];
-#pragma unroll
-            for (int t = 1; t < EXT_W2; t++) xv = (t0 == (uint32_t)t) ? x[t] : xv;
-            return kk + 4 * t0 + ((uint32_t)__builtin_ctz(xv) >> 3);
-        }
+        const uint32_t m = dmx_first_diff_bit<EXT_W2>(x);
+        if (m != 0xFFFFFFFFu) return kk + (m >> 3);
         kk += 4 * EXT_W2;
         if (kk >= lim) return kk;
     }
@@ -418,6 +406,11 @@ __device__ __forceinline__ uint32_t lds_ld(uint32_t* p) {
 }
 __device__ __forceinline__ void lds_st(uint32_t* p, uint32_t v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// Set bits of a wave mask below the calling lane (v_mbcnt_lo + v_mbcnt_hi).
+__device__ __forceinline__ uint32_t lanes_below(uint64_t m) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 
 // Inclusive prefix sum over the wave: DPP row shifts inside each row of 16, row totals by readlane.
@@ -662,7 +655,7 @@ __device__ __forceinline__ void store_short(MatchLDS& L, uint32_t k, uint32_t i,
 // extends jw from LDS.  A farther candidate must be strictly longer, so it must equal the
 // CBS bytes and the byte at the best length: that byte is tested first (one read), the
 // CBS bytes only for the rare survivors.  Then the entry's result is stored.
-template <bool DICT, bool RUNS>
+template <bool DICT, bool RUNS, int KT = KE>
 __device__ __forceinline__ void ext_queue(MatchLDS& L, uint32_t bn, uint32_t K, uint32_t* Qw, uint32_t qn,
                                           uint32_t lane, const uint32_t* __restrict__ hbk, uint32_t head = 0,
                                           uint32_t qmask = 63) {
@@ -678,22 +671,44 @@ __device__ __forceinline__ void ext_queue(MatchLDS& L, uint32_t bn, uint32_t K, 
         // distance 1 (runs): the length is where the run ends, from the change bitmap
         uint32_t bl = min(q + 1u == i && RUNS ? run_len(L, i, lim) : ext_len(L, i, q, CBS, lim), lim);
         if (bl < lim) {
-            // the byte test of every farther candidate at once (independent LDS reads)
-            const uint32_t ib = D8[i + bl], j0 = bj + 1u;
+            // the byte test of every farther candidate at once (independent LDS reads).  The
+            // tests run past the chain's end (j > nc: entries of other chains, any byte) and the
+            // mask drops those once; only a batch holding one of the first 2 KT - 1 entries of
+            // S clamps the entry index, which would otherwise fall below entry 0.  KT >= K: a
+            // caller that knows K at compile time runs K - 1 tests, not KE - 1.
+            uint32_t ib = D8[i + bl];
+            const uint32_t j0 = bj + 1u;
             uint32_t surv = 0;
+            if (__ballot(k < 2u * KT - 1u)) {
 #pragma unroll
-            for (uint32_t t = 0; t < KE - 1; t++) {
-                const uint32_t j = j0 + t;
-                const uint32_t qj = L.sorted[k - min(j, nc)];
-                surv |= (j <= nc && D8[qj + bl] == ib) ? 1u << t : 0u;
+                for (uint32_t t = 0; t < KT - 1; t++) {
+                    const uint32_t qj = L.sorted[k - min(j0 + t, nc)];
+                    surv |= D8[qj + bl] == ib ? 1u << t : 0u;
+                }
+            } else {
+#pragma unroll
+                for (uint32_t t = 0; t < KT - 1; t++) {
+                    const uint32_t qj = L.sorted[k - j0 - t];
+                    surv |= D8[qj + bl] == ib ? 1u << t : 0u;
+                }
             }
-            while (surv && bl < lim) {   // rare: test the CBS bytes, then extend
-                const uint32_t j = j0 + (uint32_t)__builtin_ctz(surv);
-                surv &= surv - 1u;
-                const uint32_t qj = L.sorted[k - j];
-                if (D8[qj + bl] != D8[i + bl] || ld8(L.data, qj) != ld8(L.data, i)) continue;
-                const uint32_t len = min(ext_len(L, i, qj, CBS, lim), lim);
-                if (len > bl) { bl = len; bj = j; }
+            surv &= (1u << (nc - bj)) - 1u;   // j0 + t <= nc  <=>  t < nc - bj (0..KT - 1)
+            if (surv) {   // rare: test the CBS bytes, then extend
+                const uint64_t own = ld8(L.data, i);
+                bool fresh = true;   // bl as the batched test saw it: the byte at bl is known equal
+                do {
+                    const uint32_t j = j0 + (uint32_t)__builtin_ctz(surv);
+                    surv &= surv - 1u;
+                    const uint32_t qj = L.sorted[k - j];
+                    if ((!fresh && D8[qj + bl] != ib) || ld8(L.data, qj) != own) continue;
+                    const uint32_t len = min(ext_len(L, i, qj, CBS, lim), lim);
+                    if (len > bl) {
+                        bl = len;
+                        bj = j;
+                        fresh = false;
+                        ib = D8[i + bl];
+                    }
+                } while (surv && bl < lim);
             }
         }
         store_short<DICT>(L, k, i, bl, bj, hbk);
@@ -916,7 +931,8 @@ __device__ __forceinline__ uint32_t search_quads(MatchLDS& L, uint32_t bn, uint3
     // search, adjacent in MatchLDS): a chunk's items go in at once, batches of 64 come out
     uint32_t* Qw = L.tsm + (wave << 7);
     uint32_t qh = 0;   // ring head (wave-uniform)
-    const uint64_t lt = (1ull << lane) - 1ull;
+    // pos + CBS < bn  <=>  pos < bnc, pos + CBS > bn  <=>  pos > bnc (signed: bn may be below CBS)
+    const int bnc = (int)bn - (int)CBS;
     uint32_t qn = 0, iters = 0;
     uint32_t cnext = wave_claim(&L.ntok);   // chunks from the workgroup counter, one ahead (search_pairs)
     for (;;) {
@@ -929,7 +945,7 @@ __device__ __forceinline__ uint32_t search_quads(MatchLDS& L, uint32_t bn, uint3
         bool act[4];
 #pragma unroll
         for (int r = 0; r < 4; r++) act[r] = more && own && k0 + (uint32_t)r < nvalid;
-        uint32_t key[4] = {0, 0, 0, 0}, lim[4] = {0, 0, 0, 0}, pos[4] = {0, 0, 0, 0};
+        uint32_t key[4] = {0, 0, 0, 0}, pos[4] = {0, 0, 0, 0};
         if (more) {
             uint32_t e[8];
             {   // the four positions in one aligned 8-byte LDS word, then their first 8 bytes
@@ -944,9 +960,6 @@ __device__ __forceinline__ uint32_t search_quads(MatchLDS& L, uint32_t bn, uint3
                     e[2 * r + 1] = (uint32_t)(v >> 32);
                 }
             }
-#pragma unroll
-            for (int r = 0; r < 4; r++)
-                if (act[r]) lim[r] = (bn - pos[r]) < MAXLEN ? (bn - pos[r]) : MAXLEN;
             iters += 4 * KK;
             {   // sort check: E_0 after E_3 of the lane below, E_r after E_(r-1)
                 uint32_t sk[4];
@@ -962,18 +975,27 @@ __device__ __forceinline__ uint32_t search_quads(MatchLDS& L, uint32_t bn, uint3
                 (void)bad;
 #endif
             }
-            if (base == 0) {
-                uint32_t nc[4];
+            // the length limits are needed only where they can cap a register compare: the first
+            // chunk and chunks holding one of the last CBS - 1 positions (pos + CBS > bn).  The
+            // halo lanes' positions count too: the clamped steps give an uncapped entry the same
+            // key, so a chunk more on that path changes nothing, and one max serves all four.
+            if (base == 0 ||
+                __builtin_amdgcn_ballot_w64((int)max(max(pos[0], pos[1]), max(pos[2], pos[3])) > bnc)) {
+                uint32_t lim[4];
 #pragma unroll
-                for (int r = 0; r < 4; r++) nc[r] = min(k0 + (uint32_t)r, (uint32_t)KK);
-                quad_steps<KK, true, true, true>(e, key, nc, lim);
-            } else if (__ballot((act[0] && lim[0] < CBS) || (act[1] && lim[1] < CBS) || (act[2] && lim[2] < CBS) ||
-                                (act[3] && lim[3] < CBS))) {
-                const uint32_t nc[4] = {KK, KK, KK, KK};
-                quad_steps<KK, true, false, true>(e, key, nc, lim);
+                for (int r = 0; r < 4; r++) lim[r] = act[r] ? min(bn - pos[r], (uint32_t)MAXLEN) : 0u;
+                if (base == 0) {
+                    uint32_t nc[4];
+#pragma unroll
+                    for (int r = 0; r < 4; r++) nc[r] = min(k0 + (uint32_t)r, (uint32_t)KK);
+                    quad_steps<KK, true, true, true>(e, key, nc, lim);
+                } else {
+                    const uint32_t nc[4] = {KK, KK, KK, KK};
+                    quad_steps<KK, true, false, true>(e, key, nc, lim);
+                }
             } else {
                 const uint32_t nc[4] = {0, 0, 0, 0};
-                quad_steps<KK, false, false, false>(e, key, nc, lim);
+                quad_steps<KK, false, false, false>(e, key, nc, nc);
             }
         }
         // a candidate equal in all CBS bytes (key >= 64): the entry is queued for the LDS
@@ -986,9 +1008,9 @@ __device__ __forceinline__ uint32_t search_quads(MatchLDS& L, uint32_t bn, uint3
 #ifdef DMX_KO_QUEUE   // timing knockout (wrong output): no queued extension
             push[r] = false;
 #else
-            push[r] = act[r] && key[r] >= (CBS << 3) && lim[r] > CBS;
+            push[r] = act[r] && key[r] >= (CBS << 3) && (int)pos[r] < bnc;   // (the limit is past CBS)
 #endif
-            pmv[r] = __ballot(push[r]);
+            pmv[r] = __builtin_amdgcn_ballot_w64(push[r]);   // (__ballot goes through an int and a compare)
             npr[r] = (uint32_t)__popcll(pmv[r]);
         }
         const uint32_t npt = npr[0] + npr[1] + npr[2] + npr[3];
@@ -1003,7 +1025,7 @@ __device__ __forceinline__ uint32_t search_quads(MatchLDS& L, uint32_t bn, uint3
                 if (qn >= 64u || (qn && (!more || qn + want > 128u))) {
                     const uint32_t nq = qn < 64u ? qn : 64u;
                     const uint64_t td0 = stamp ? __builtin_amdgcn_s_memtime() : 0;
-                    ext_queue<DICT, false>(L, bn, KK, Qw, nq, lane, hbk, qh, 127u);
+                    ext_queue<DICT, false, KK>(L, bn, KK, Qw, nq, lane, hbk, qh, 127u);
                     if (stamp) tdef += __builtin_amdgcn_s_memtime() - td0;
                     qh += nq;
                     qn -= nq;
@@ -1015,7 +1037,7 @@ __device__ __forceinline__ uint32_t search_quads(MatchLDS& L, uint32_t bn, uint3
                 for (uint32_t r = 0; r < 4; r++) {
                     if (rs == 4u || rs == r) {
                         if (push[r])
-                            lds_st(&Qw[(qh + qn + off + (uint32_t)__popcll(pmv[r] & lt)) & 127u],
+                            lds_st(&Qw[(qh + qn + off + lanes_below(pmv[r])) & 127u],
                                    (k0 + r) | ((8u - (key[r] & 7u)) << 15));
                         off += npr[r];
                     }
