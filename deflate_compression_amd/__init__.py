@@ -16,6 +16,7 @@ include/dmx.h).  This module is a thin ctypes layer:
     bgzf_read_ranges(zt, ranges) / bgzf_pread(zt, off, n) byte ranges of such a file: only the members they touch are decoded
     inflate_batch(streams)                                many independent zlib / gzip / raw DEFLATE streams, side by side
                                                           (zdict=: preset dictionaries, zlib's FDICT / inflateSetDictionary)
+    inflate_parallel_plan_host(z)                         ONE zlib / gzip / raw stream cut at true block starts (host)
     compress_batch(bufs)                                  many independent buffers into as many streams, in one chain of launches
     Encoder                                               device-resident encodes
 
@@ -39,6 +40,7 @@ __all__ = [
     "inflate_batch_dict_async", "inflate_dict_host", "BDict", "DMX_BATCH_NODICT",
     "compress_batch", "compress_batch_async", "encode_batch_blocks", "EStream", "EResult", "EBatchStatus", "ERESULT_DTYPE",
     "compress_batch_dict_async",
+    "inflate_parallel_plan_host", "PChunk", "ParStatus", "PCHUNK_DTYPE",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -138,6 +140,23 @@ class BDict(ctypes.Structure):
     _fields_ = [("off", ctypes.c_uint64), ("len", ctypes.c_uint64)]
 
 
+class PChunk(ctypes.Structure):
+    """dmx_pchunk: one live chunk of dmx_inflate_parallel_plan_host -- its blocks' bits and its output range"""
+    _fields_ = [("bit", ctypes.c_uint64), ("end_bit", ctypes.c_uint64), ("out_off", ctypes.c_uint64),
+                ("out_len", ctypes.c_uint64)]
+
+
+class ParStatus(ctypes.Structure):
+    """dmx_par_status: the 56-byte record of dmx_inflate_parallel_plan_host"""
+    _fields_ = [("status", ctypes.c_int32), ("format", ctypes.c_uint32), ("out_len", ctypes.c_uint64),
+                ("in_used", ctypes.c_uint64), ("check", ctypes.c_uint32), ("nchunks", ctypes.c_uint32),
+                ("ncand", ctypes.c_uint32), ("nlive", ctypes.c_uint32), ("ndead", ctypes.c_uint32),
+                ("gave_up", ctypes.c_uint32), ("work_len", ctypes.c_uint64)]
+
+
+# numpy's view of dmx_pchunk records
+PCHUNK_DTYPE = [("bit", "<u8"), ("end_bit", "<u8"), ("out_off", "<u8"), ("out_len", "<u8")]
+
 # numpy's view of dmx_bresult records
 BRESULT_DTYPE = [("status", "<i4"), ("format", "<u4"), ("out_len", "<u8"), ("in_used", "<u8"), ("check", "<u4"),
                  ("reserved", "<u4")]
@@ -226,6 +245,7 @@ def lib() -> ctypes.CDLL:
                                          ctypes.c_int),
         "dmx_inflate_dict_host": ([vp, u64, u32, vp, u64, ctypes.POINTER(vp), ctypes.POINTER(u64), ctypes.POINTER(u64)],
                                   ctypes.c_int),
+        "dmx_inflate_parallel_plan_host": ([vp, u64, u32, u32, vp, u32, ctypes.POINTER(ParStatus)], ctypes.c_int),
         "dmx_encode_batch_blocks": ([u64, u32, i32], u32),
         "dmx_encode_batch_bound": ([u64, u32, i32, u32], u64),
         "dmx_ctx_reserve_batch": ([vp, u32, u32, i32, u32], ctypes.c_int),
@@ -877,6 +897,31 @@ def inflate_batch(z, streams=None, fmt: str = "auto", sizes=None, strict: bool =
     if strict and rec.nfailed:
         raise DeflateError(int(results["status"][rec.first_bad]), f"inflate_batch: stream {rec.first_bad}")
     return out[:total], offsets, results
+
+
+def _par_info(rec: ParStatus) -> dict:
+    return {f: int(getattr(rec, f)) for f, _ in ParStatus._fields_}
+
+
+def inflate_parallel_plan_host(z, fmt: str = "auto", chunk_bytes: int | None = None):
+    """One zlib stream, gzip member or raw DEFLATE stream cut into chunks that begin at true block
+    boundaries, with their output ranges, on the host (dmx_inflate_parallel_plan_host): returns
+    (chunks, info) -- the live chunks as a numpy array of PCHUNK_DTYPE records and the record's
+    fields as a dict (status included: a stream the plan refuses is not an exception here)."""
+    import numpy as np
+    if fmt not in _BATCH_FMT:
+        raise ValueError("fmt is one of " + ", ".join(_BATCH_FMT))
+    zp, zn, zk = _buf(z)
+    rec = ParStatus()
+    cb = int(chunk_bytes or 0)
+    r = lib().dmx_inflate_parallel_plan_host(zp, zn, _BATCH_FMT[fmt], cb, None, 0, ctypes.byref(rec))
+    chunks = np.zeros(rec.nlive if r in (0, -E["E_SZ"]) else 0, dtype=PCHUNK_DTYPE)
+    if r == -E["E_SZ"]:
+        r = lib().dmx_inflate_parallel_plan_host(zp, zn, _BATCH_FMT[fmt], cb, ctypes.c_void_p(chunks.ctypes.data),
+                                                 chunks.shape[0], ctypes.byref(rec))
+    del zk
+    _check(r, "dmx_inflate_parallel_plan_host")
+    return chunks, _par_info(rec)
 
 
 _EBATCH_FMT = {"zlib": DMX_ZLIB, "gzip": DMX_GZIP, "raw": DMX_F_FINAL}

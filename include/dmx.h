@@ -679,6 +679,41 @@ int dmx_inflate_batch_dict_async(const void* d_z, uint64_t zbytes, const dmx_bst
  * with dict_len > 0, fmt above 3), -E_MALLOC, or the stream's status. */
 int dmx_inflate_dict_host(const void* z, uint64_t n, uint32_t fmt, const void* dict, uint64_t dict_len,
                           void** out, uint64_t* out_len, uint64_t* in_used);
+/* One foreign stream, cut for many decoders: the plan (csrc/dmx_inflate_par_host.cpp, csrc/dmx_pfind.h;
+ * DESIGN.md §3.1 "One foreign stream").  A single zlib stream, gzip member or raw DEFLATE stream
+ * that carries no block index -- what gzip, pigz, zlib, a Parquet or an HTTP writer leave -- is cut
+ * into chunks that start at true block boundaries and whose output lengths are known, which is what
+ * a parallel decode needs; the scheme is the one pugz and rapidgzip use on CPUs, with every
+ * speculative step checked.  Host only, no GPU; the text of the search, the landing rule and the
+ * walk (dmx_pfind.h) compiles for the device too.
+ *   the framing gives chunk 0 its start (the first block); the compressed bytes are cut every
+ *   chunk_bytes (0: 16 384; 1024..2^30) and every chunk is searched for the first bit offset at
+ *   which a non-final dynamic block can start: a cheap filter (BFINAL 0, BTYPE 2, HLIT and HDIST at
+ *   most 29, the code length code exactly complete), then the decoder's own header rules in full;
+ *   a chunk with such a candidate is decoded from it for lengths only (the window taken as primed:
+ *   no distance is too far), block after block, until a block boundary is exactly a later
+ *   candidate; candidates it oversteps are false and are passed -- more than 8 of them, or more
+ *   than 4 MiB produced, and the walk is lost; a walk from chunk 0 along the landings keeps the
+ *   chunks it reaches.  A chunk is live iff that walk reaches it, so every live chunk began at a
+ *   true block boundary; the others are dead, whatever they decoded.  Stored and fixed blocks are
+ *   not searched for: a stream without dynamic blocks is one live chunk.
+ * chunks receives at most cap live chunks in stream order (out_off is the exclusive scan of
+ * out_len; end_bit of one is bit of the next); -E_SZ where there are more (st->nlive says how many).
+ * The record (56 bytes): status 0 or -E_* (the framing's, or a live chunk's first error; distances
+ * before the first output byte and the trailer's check value are a decode's to find); format the
+ * framing (1, 2, 3); out_len; in_used through the trailer; check the stored Adler-32 / CRC-32;
+ * nchunks, ncand (chunks with a candidate, chunk 0 included), nlive, ndead = ncand - nlive;
+ * gave_up = 1 with -E_RANGE where a live walk was lost; work_len the scratch a decode into 16-bit
+ * cells would need.  After an error out_len, in_used, check and work_len are 0.  zbytes and the
+ * output are at most 0xFFFFFFF0, else -E_RANGE.  Returns 0 with the record in *st, -E_INVAL
+ * (st NULL, z NULL with zbytes > 0, chunks NULL with cap > 0, fmt above 3, chunk_bytes out of
+ * range), -E_RANGE, -E_MALLOC or -E_SZ. */
+typedef struct { uint64_t bit, end_bit, out_off, out_len; } dmx_pchunk;          /* 32 bytes: a live chunk */
+typedef struct { int32_t status; uint32_t format; uint64_t out_len; uint64_t in_used;
+                 uint32_t check; uint32_t nchunks, ncand, nlive, ndead; uint32_t gave_up;
+                 uint64_t work_len; } dmx_par_status;                             /* 56 bytes */
+int dmx_inflate_parallel_plan_host(const void* z, uint64_t zbytes, uint32_t fmt, uint32_t chunk_bytes,
+                                   dmx_pchunk* chunks, uint32_t cap, dmx_par_status* st);
 /* Batches of independent buffers into independent streams (csrc/dmx_encode_batch.hip):
  * the encode's counterpart of dmx_inflate_batch_async.  nstreams buffers become nstreams complete
  * zlib streams, gzip members or raw DEFLATE streams, every one decodable on its own, in one chain of
