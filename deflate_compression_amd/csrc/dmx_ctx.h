@@ -78,7 +78,7 @@ struct dmx_ctx {
     void* bplan;          // the plan's scratch for cap_bstreams streams: head, tile sums, block starts
     uint64_t cap_bstreams;
     int last_batch;       // the last encode was a batch (dmx_block_index: -E_INVAL)
-    // batch encodes against dictionaries (dmx_encode_batch_dict.hip; dmx_ctx_reserve_batch_dict only)
+    // batch encodes against dictionaries (dmx_encode_batch_dict_async; dmx_ctx_reserve_batch_dict only)
     uint32_t* bdictid;    // cap_bdicts DICTIDs: the dictionaries' Adler-32s of the call in flight
     uint64_t cap_bdicts;
     uint64_t chain_dicts; // chain slots kept beyond a slot per block and the single encode's one

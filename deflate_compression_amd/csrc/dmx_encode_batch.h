@@ -1,6 +1,7 @@
-// dmx_encode_batch.h -- the plan of a batch encode (dmx_encode_batch_async), stage by
-// stage: what one thread of every planning kernel does, so that the kernels of dmx_encode_batch.hip
-// and the loops of the host twin (tests/c/encode_batch_model.cpp) run the same text.  The collectives
+// dmx_encode_batch.h -- the plan of a batch encode (dmx_encode_batch_async and
+// dmx_encode_batch_dict_async), stage by stage: what one thread of every planning
+// kernel does, so that the kernels of dmx_encode_batch.hip and the loops of the host twins
+// (tests/c/encode_batch_model.cpp, tests/c/encode_batch_dict_model.cpp) run the same text.  The collectives
 // between the per-thread parts -- the sums and the exclusive scan over a workgroup -- are the
 // caller's: LDS on the device, a loop in the twin.  Host and device, C++ only, internal.
 #ifndef DMX_ENCODE_BATCH_H
@@ -51,27 +52,86 @@ DMX_EB_HD static inline uint64_t dmx_eb_sat(uint64_t a, uint64_t b) {
     return s < a ? ~0ull : s;
 }
 
+// ---- A stream's verdict.  dmx_encode_batch_dict_async's also depends on the stream's preset dictionary,
+// so the plan is written once, with a dmx_ebd; dmx_encode_batch_async passes the empty one
+// (dmx_ebd_none), under which every stream is DMX_BATCH_NODICT and the verdict is dmx_eb_valid alone.
+// The dmx_eb_* forms without a dmx_ebd are that call (the host twin of the plain batch runs them).
+struct dmx_ebd {
+    const dmx_bdict* dicts;    // ndicts records into d_dict[0, dict_bytes)
+    const uint32_t* dict_of;   // per stream: an index or DMX_BATCH_NODICT; NULL: every stream uses 0
+    uint64_t dict_bytes;
+    uint32_t ndicts;
+    uint32_t fdict;            // DMX_F_FDICT: the header names the dictionary, which is then whole
+};
+DMX_EB_HD static inline dmx_ebd dmx_ebd_none() {
+    dmx_ebd d = {NULL, NULL, 0, 0, 0};
+    return d;
+}
 // stream k lies inside d_in[0, in_bytes): the test that cannot wrap
 DMX_EB_HD static inline bool dmx_eb_valid(const dmx_estream& s, uint64_t in_bytes) {
     return s.in_off <= in_bytes && s.in_len <= in_bytes - s.in_off;
 }
+// the dictionary stream k names: an index, or DMX_BATCH_NODICT (also every stream of a call without
+// dictionaries and without d_dict_of) -- dmx_inflate_batch_dict_async's rule
+DMX_EB_HD static inline uint32_t dmx_ebd_index(const dmx_ebd& d, uint32_t k) {
+    return d.dict_of ? d.dict_of[k] : d.ndicts ? 0u : DMX_BATCH_NODICT;
+}
+// record j lies inside d_dict[0, dict_bytes): the test that cannot wrap
+DMX_EB_HD static inline bool dmx_ebd_inside(const dmx_bdict& r, uint64_t dict_bytes) {
+    return r.off <= dict_bytes && r.len <= dict_bytes - r.off;
+}
+// stream k's status: -E_RANGE for a buffer outside d_in, a dictionary index at or above ndicts or a
+// record outside d_dict; under DMX_F_FDICT -E_INVAL for a dictionary of length 0 or above sw, the
+// single encode's verdict (its DICTID must cover what the parse may reference); else 0
+DMX_EB_HD static inline int32_t dmx_ebd_status(const dmx_estream* st, uint32_t k, uint64_t in_bytes, uint32_t sw,
+                                               const dmx_ebd& d) {
+    if (!dmx_eb_valid(st[k], in_bytes)) return -(int32_t)E_RANGE;
+    const uint32_t di = dmx_ebd_index(d, k);
+    if (di == DMX_BATCH_NODICT) return 0;
+    if (di >= d.ndicts || !dmx_ebd_inside(d.dicts[di], d.dict_bytes)) return -(int32_t)E_RANGE;
+    if (d.fdict && (d.dicts[di].len < 1 || d.dicts[di].len > sw)) return -(int32_t)E_INVAL;
+    return 0;
+}
+// the history of a first block: the last min(len, sw) bytes of the stream's dictionary (hn 0: none),
+// at d_dict + *off, its chain slot *slot = the dictionary's index.  For a stream with status 0.
+DMX_EB_HD static inline uint32_t dmx_ebd_history(const dmx_ebd& d, uint32_t k, uint32_t sw, uint64_t* off, uint32_t* slot) {
+    const uint32_t di = dmx_ebd_index(d, k);
+    *off = 0;
+    *slot = 0;
+    if (di == DMX_BATCH_NODICT) return 0;
+    const dmx_bdict r = d.dicts[di];
+    const uint32_t hn = r.len < sw ? (uint32_t)r.len : sw;
+    *off = r.off + (r.len - hn);
+    *slot = di;
+    return hn;
+}
 // blocks of a stream: an empty one has one (empty) block, which carries its whole framing; a stream
-// that is -E_RANGE has none
+// that is refused has none
+DMX_EB_HD static inline uint64_t dmx_eb_nblocks(bool ok, uint64_t len, uint32_t sw) {
+    const uint64_t c = len / sw + (len % sw ? 1u : 0u);
+    return !ok ? 0u : c ? c : 1u;
+}
+DMX_EB_HD static inline uint64_t dmx_ebd_count(const dmx_estream* st, uint32_t k, uint64_t in_bytes, uint32_t sw,
+                                               const dmx_ebd& d) {
+    return dmx_eb_nblocks(dmx_ebd_status(st, k, in_bytes, sw, d) == 0, st[k].in_len, sw);
+}
 DMX_EB_HD static inline uint64_t dmx_eb_count(const dmx_estream& s, uint64_t in_bytes, uint32_t sw) {
-    if (!dmx_eb_valid(s, in_bytes)) return 0;
-    const uint64_t c = s.in_len / sw + (s.in_len % sw ? 1u : 0u);
-    return c ? c : 1u;
+    return dmx_ebd_count(&s, 0, in_bytes, sw, dmx_ebd_none());
 }
 
 // ---- dmx_eb_count_kernel: a thread per stream; the caller sums the four over the tile
-DMX_EB_HD static inline dmx_eb_tile dmx_eb_stream_sums(const dmx_estream* st, uint32_t k, uint64_t in_bytes, uint32_t sw) {
+DMX_EB_HD static inline dmx_eb_tile dmx_ebd_stream_sums(const dmx_estream* st, uint32_t k, uint64_t in_bytes, uint32_t sw,
+                                                        const dmx_ebd& d) {
     dmx_eb_tile t;
-    const bool ok = dmx_eb_valid(st[k], in_bytes);
-    t.blocks = dmx_eb_count(st[k], in_bytes, sw);
+    const bool ok = dmx_ebd_status(st, k, in_bytes, sw, d) == 0;
+    t.blocks = dmx_eb_nblocks(ok, st[k].in_len, sw);
     t.bytes = ok ? st[k].in_len : 0u;
     t.nfailed = ok ? 0u : 1u;
     t.first_bad = ok ? DMX_EB_NOBAD : k;
     return t;
+}
+DMX_EB_HD static inline dmx_eb_tile dmx_eb_stream_sums(const dmx_estream* st, uint32_t k, uint64_t in_bytes, uint32_t sw) {
+    return dmx_ebd_stream_sums(st, k, in_bytes, sw, dmx_ebd_none());
 }
 DMX_EB_HD static inline dmx_eb_tile dmx_eb_tile_add(const dmx_eb_tile& a, const dmx_eb_tile& b) {
     dmx_eb_tile t;
@@ -127,19 +187,25 @@ DMX_EB_HD static inline void dmx_eb_decide(dmx_eb_head* head, const dmx_eb_tile&
 // the tile's prefix plus the streams before k in its tile, saturating); the thread of the last
 // stream also writes starts[nstreams].  Then the stream's record before any kernel encodes: its
 // status and block count (out_off, out_len and check come from the finish).
-DMX_EB_HD static inline void dmx_eb_start(const dmx_estream* st, uint32_t k, uint32_t nstreams, uint64_t in_bytes,
-                                          uint32_t sw, uint64_t before, uint64_t* starts, dmx_eresult* res) {
-    const uint64_t c = dmx_eb_count(st[k], in_bytes, sw);
+DMX_EB_HD static inline void dmx_ebd_start(const dmx_estream* st, uint32_t k, uint32_t nstreams, uint64_t in_bytes,
+                                           uint32_t sw, const dmx_ebd& d, uint64_t before, uint64_t* starts,
+                                           dmx_eresult* res) {
+    const int32_t status = dmx_ebd_status(st, k, in_bytes, sw, d);
+    const uint64_t c = dmx_eb_nblocks(status == 0, st[k].in_len, sw);
     starts[k] = before;
     if (k + 1 == nstreams) starts[nstreams] = dmx_eb_sat(before, c);
     dmx_eresult r;
-    r.status = dmx_eb_valid(st[k], in_bytes) ? 0 : -(int32_t)E_RANGE;
+    r.status = status;
     r.nblocks = c > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)c;
     r.out_off = 0;
     r.out_len = 0;
     r.check = 0;
     r.reserved = 0;
     res[k] = r;
+}
+DMX_EB_HD static inline void dmx_eb_start(const dmx_estream* st, uint32_t k, uint32_t nstreams, uint64_t in_bytes,
+                                          uint32_t sw, uint64_t before, uint64_t* starts, dmx_eresult* res) {
+    dmx_ebd_start(st, k, nstreams, in_bytes, sw, dmx_ebd_none(), before, starts, res);
 }
 
 // the stream that block b belongs to: the last k of 0..nstreams-1 with starts[k] <= b (nstreams >= 1,
@@ -157,9 +223,11 @@ DMX_EB_HD static inline uint32_t dmx_eb_find(const uint64_t* starts, uint32_t ns
 }
 
 // ---- dmx_eb_table_kernel: a thread per table entry b < max_blocks.  Entries at or beyond the real
-// block count, and every entry of a batch that does not fit max_blocks, are void.
-DMX_EB_HD static inline dmx_bblk dmx_eb_entry(const dmx_estream* st, const uint64_t* starts, uint32_t nstreams,
-                                              const dmx_eb_head* head, uint32_t sw, uint32_t b) {
+// block count, and every entry of a batch that does not fit max_blocks, are void.  starts[] already
+// holds the verdict: a refused stream has no blocks, so no entry finds it.  DMX_BB_DICT: the
+// entry's stream names a dictionary.
+DMX_EB_HD static inline dmx_bblk dmx_ebd_entry(const dmx_estream* st, const uint64_t* starts, uint32_t nstreams,
+                                               const dmx_eb_head* head, uint32_t sw, const dmx_ebd& d, uint32_t b) {
     dmx_bblk e;
     e.off = 0;
     e.len = DMX_BB_VOID;
@@ -170,9 +238,14 @@ DMX_EB_HD static inline dmx_bblk dmx_eb_entry(const dmx_estream* st, const uint6
     const uint64_t cnt = len / sw + (len % sw ? 1u : 0u);   // (0 for the empty stream's one block)
     const uint64_t left = len - j * sw;
     e.off = st[k].in_off + j * sw;
-    e.len = (uint32_t)(left < sw ? left : sw) | (j == 0 ? DMX_BB_FIRST : 0u) | (j + 1 >= cnt ? DMX_BB_LAST : 0u);
+    e.len = (uint32_t)(left < sw ? left : sw) | (j == 0 ? DMX_BB_FIRST : 0u) | (j + 1 >= cnt ? DMX_BB_LAST : 0u) |
+            (dmx_ebd_index(d, k) != DMX_BATCH_NODICT ? DMX_BB_DICT : 0u);
     e.stream = k;
     return e;
+}
+DMX_EB_HD static inline dmx_bblk dmx_eb_entry(const dmx_estream* st, const uint64_t* starts, uint32_t nstreams,
+                                              const dmx_eb_head* head, uint32_t sw, uint32_t b) {
+    return dmx_ebd_entry(st, starts, nstreams, head, sw, dmx_ebd_none(), b);
 }
 
 // The bytes the batch's streams may need at most, packed: stream k at most
@@ -183,88 +256,6 @@ DMX_EB_HD static inline uint32_t dmx_eb_blocks_bound(uint64_t total_in, uint32_t
     // sum of max(1, ceil(len / sw)) <= total / sw + nstreams (a partial or empty block per stream)
     const uint64_t b = dmx_eb_sat(total_in / sw, nstreams);
     return b > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)b;
-}
-
-// ---- dmx_encode_batch_dict_async: the same plan where a stream's verdict also depends on its preset
-// dictionary.  The functions above keep their signatures (the host twin of the plain batch runs
-// them); these sit beside them and the kernels of the dictionary batch call these instead.
-struct dmx_ebd {
-    const dmx_bdict* dicts;    // ndicts records into d_dict[0, dict_bytes)
-    const uint32_t* dict_of;   // per stream: an index or DMX_BATCH_NODICT; NULL: every stream uses 0
-    uint64_t dict_bytes;
-    uint32_t ndicts;
-    uint32_t fdict;            // DMX_F_FDICT: the header names the dictionary, which is then whole
-};
-// the dictionary stream k names: an index, or DMX_BATCH_NODICT (also every stream of a call without
-// dictionaries and without d_dict_of) -- dmx_inflate_batch_dict_async's rule
-DMX_EB_HD static inline uint32_t dmx_ebd_index(const dmx_ebd& d, uint32_t k) {
-    return d.dict_of ? d.dict_of[k] : d.ndicts ? 0u : DMX_BATCH_NODICT;
-}
-// record j lies inside d_dict[0, dict_bytes): the test that cannot wrap
-DMX_EB_HD static inline bool dmx_ebd_inside(const dmx_bdict& r, uint64_t dict_bytes) {
-    return r.off <= dict_bytes && r.len <= dict_bytes - r.off;
-}
-// stream k's status: -E_RANGE for a buffer outside d_in, a dictionary index at or above ndicts or a
-// record outside d_dict; under DMX_F_FDICT -E_INVAL for a dictionary of length 0 or above sw, the
-// single encode's verdict (its DICTID must cover what the parse may reference); else 0
-DMX_EB_HD static inline int32_t dmx_ebd_status(const dmx_estream* st, uint32_t k, uint64_t in_bytes, uint32_t sw,
-                                               const dmx_ebd& d) {
-    if (!dmx_eb_valid(st[k], in_bytes)) return -(int32_t)E_RANGE;
-    const uint32_t di = dmx_ebd_index(d, k);
-    if (di == DMX_BATCH_NODICT) return 0;
-    if (di >= d.ndicts || !dmx_ebd_inside(d.dicts[di], d.dict_bytes)) return -(int32_t)E_RANGE;
-    if (d.fdict && (d.dicts[di].len < 1 || d.dicts[di].len > sw)) return -(int32_t)E_INVAL;
-    return 0;
-}
-// the history of a first block: the last min(len, sw) bytes of the stream's dictionary (hn 0: none),
-// at d_dict + *off, its chain slot *slot = the dictionary's index.  For a stream with status 0.
-DMX_EB_HD static inline uint32_t dmx_ebd_history(const dmx_ebd& d, uint32_t k, uint32_t sw, uint64_t* off, uint32_t* slot) {
-    const uint32_t di = dmx_ebd_index(d, k);
-    *off = 0;
-    *slot = 0;
-    if (di == DMX_BATCH_NODICT) return 0;
-    const dmx_bdict r = d.dicts[di];
-    const uint32_t hn = r.len < sw ? (uint32_t)r.len : sw;
-    *off = r.off + (r.len - hn);
-    *slot = di;
-    return hn;
-}
-DMX_EB_HD static inline uint64_t dmx_ebd_count(const dmx_estream* st, uint32_t k, uint64_t in_bytes, uint32_t sw,
-                                               const dmx_ebd& d) {
-    return dmx_ebd_status(st, k, in_bytes, sw, d) ? 0u : dmx_eb_count(st[k], in_bytes, sw);
-}
-// dmx_eb_stream_sums, dmx_eb_start and dmx_eb_entry with the dictionary's verdict
-DMX_EB_HD static inline dmx_eb_tile dmx_ebd_stream_sums(const dmx_estream* st, uint32_t k, uint64_t in_bytes, uint32_t sw,
-                                                        const dmx_ebd& d) {
-    dmx_eb_tile t;
-    const bool ok = dmx_ebd_status(st, k, in_bytes, sw, d) == 0;
-    t.blocks = ok ? dmx_eb_count(st[k], in_bytes, sw) : 0u;
-    t.bytes = ok ? st[k].in_len : 0u;
-    t.nfailed = ok ? 0u : 1u;
-    t.first_bad = ok ? DMX_EB_NOBAD : k;
-    return t;
-}
-DMX_EB_HD static inline void dmx_ebd_start(const dmx_estream* st, uint32_t k, uint32_t nstreams, uint64_t in_bytes,
-                                           uint32_t sw, const dmx_ebd& d, uint64_t before, uint64_t* starts,
-                                           dmx_eresult* res) {
-    const uint64_t c = dmx_ebd_count(st, k, in_bytes, sw, d);
-    starts[k] = before;
-    if (k + 1 == nstreams) starts[nstreams] = dmx_eb_sat(before, c);
-    dmx_eresult r;
-    r.status = dmx_ebd_status(st, k, in_bytes, sw, d);
-    r.nblocks = c > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)c;
-    r.out_off = 0;
-    r.out_len = 0;
-    r.check = 0;
-    r.reserved = 0;
-    res[k] = r;
-}
-// (starts[] already holds the dictionary's verdict: a refused stream has no blocks, so no entry finds it)
-DMX_EB_HD static inline dmx_bblk dmx_ebd_entry(const dmx_estream* st, const uint64_t* starts, uint32_t nstreams,
-                                               const dmx_eb_head* head, uint32_t sw, const dmx_ebd& d, uint32_t b) {
-    dmx_bblk e = dmx_eb_entry(st, starts, nstreams, head, sw, b);
-    if (!(e.len & DMX_BB_VOID) && dmx_ebd_index(d, e.stream) != DMX_BATCH_NODICT) e.len |= DMX_BB_DICT;
-    return e;
 }
 
 #endif

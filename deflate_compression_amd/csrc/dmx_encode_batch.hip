@@ -25,6 +25,22 @@
 //                            and the stream's header and trailer ORed into the words K3 zeroed
 // No atomics but the ORs into the output: sums and minima are reductions, so nothing depends on the
 // order in which workgroups run.
+//
+// Against preset dictionaries (dmx_encode_batch_dict_async) it is the same encode (eb_run): the plan
+// with the dictionary's verdict (a dmx_ebd; the plain batch passes the empty one), K3 and the finish
+// with the stream's own header width (DB), and a history.  The bytes of stream k are the single
+// encode's for buffer k with opts->dict = its dictionary, so block 0 of a stream searches its
+// dictionary's last min(len, sw) bytes, block j >= 1 searches block j - 1 of its own stream, and no
+// block ever searches the table entry before it when that belongs to another stream.  Chain slots:
+// [0, ndicts) the dictionaries, each sorted once per call however many streams share it; ndicts + b
+// table entry b.
+//   dmx_dict_adler_kernel        the DICTIDs (DMX_F_FDICT), a kernel of the call: the dictionaries
+//                                may change between two replays of a graph
+//   dmx_ebd_chain_kernel         chain_block, the source from the table or d_dicts
+//   dmx_ebd_hist_kernel<6|7|8>   hist_search as a loop: a workgroup walks a contiguous range of
+//                                table entries and keeps a dictionary's staged history, S and
+//                                bucket ends in LDS while the next entry's history is the same slot
+//   K0 with uni_ok 0, K1 = match_block<true, 3, false, true>
 #include "dmx_encode_batch.h"
 
 #define EB_WG 256   // threads per workgroup of the plan: one stream or table entry each
@@ -70,11 +86,11 @@ __device__ static inline dmx_eb_tile eb_wg_sums(const dmx_eb_tile& v, uint64_t* 
 }
 
 __global__ __launch_bounds__(EB_WG) void dmx_eb_count_kernel(const dmx_estream* __restrict__ st, uint32_t nstreams,
-                                                             uint64_t in_bytes, uint32_t sw,
+                                                             uint64_t in_bytes, uint32_t sw, const dmx_ebd d,
                                                              dmx_eb_tile* __restrict__ tiles) {
     __shared__ uint64_t sh[EB_WG];
     const uint64_t k = (uint64_t)blockIdx.x * DMX_EB_STILE + threadIdx.x;
-    const dmx_eb_tile v = k < nstreams ? dmx_eb_stream_sums(st, (uint32_t)k, in_bytes, sw) : dmx_eb_tile_zero();
+    const dmx_eb_tile v = k < nstreams ? dmx_ebd_stream_sums(st, (uint32_t)k, in_bytes, sw, d) : dmx_eb_tile_zero();
     uint64_t before;
     const dmx_eb_tile t = eb_wg_sums(v, sh, &before);
     if (threadIdx.x == 0) tiles[blockIdx.x] = t;
@@ -92,25 +108,25 @@ __global__ __launch_bounds__(DMX_EB_STHREADS) void dmx_eb_plan_scan_kernel(dmx_e
 }
 
 __global__ __launch_bounds__(EB_WG) void dmx_eb_starts_kernel(const dmx_estream* __restrict__ st, uint32_t nstreams,
-                                                              uint64_t in_bytes, uint32_t sw,
+                                                              uint64_t in_bytes, uint32_t sw, const dmx_ebd d,
                                                               const dmx_eb_tile* __restrict__ tiles,
                                                               uint64_t* __restrict__ starts, dmx_eresult* __restrict__ res) {
     __shared__ uint64_t sh[EB_WG];
     const uint64_t k = (uint64_t)blockIdx.x * DMX_EB_STILE + threadIdx.x;
-    const uint64_t c = k < nstreams ? dmx_eb_count(st[k], in_bytes, sw) : 0u;
+    const uint64_t c = k < nstreams ? dmx_ebd_count(st, (uint32_t)k, in_bytes, sw, d) : 0u;
     uint64_t tot;
     const uint64_t before = dmx_eb_sat(tiles[blockIdx.x].blocks, eb_scan<uint64_t>(c, 0, sh, EbSat(), &tot));
-    if (k < nstreams) dmx_eb_start(st, (uint32_t)k, nstreams, in_bytes, sw, before, starts, res);
+    if (k < nstreams) dmx_ebd_start(st, (uint32_t)k, nstreams, in_bytes, sw, d, before, starts, res);
 }
 
 __global__ __launch_bounds__(EB_WG) void dmx_eb_table_kernel(const dmx_estream* __restrict__ st,
                                                              const uint64_t* __restrict__ starts, uint32_t nstreams,
                                                              const dmx_eb_head* __restrict__ head, uint32_t sw,
-                                                             uint32_t max_blocks, dmx_bblk* __restrict__ tab,
-                                                             dmx_blkinfo* __restrict__ info) {
+                                                             const dmx_ebd d, uint32_t max_blocks,
+                                                             dmx_bblk* __restrict__ tab, dmx_blkinfo* __restrict__ info) {
     const uint64_t b = (uint64_t)blockIdx.x * EB_WG + threadIdx.x;
     if (b >= max_blocks) return;
-    const dmx_bblk e = dmx_eb_entry(st, starts, nstreams, head, sw, (uint32_t)b);
+    const dmx_bblk e = dmx_ebd_entry(st, starts, nstreams, head, sw, d, (uint32_t)b);
     tab[b] = e;
     // the block record before K0 / K1: a void entry and an empty stream's block are complete here
     // (prestored 1: K1 and K2 leave them alone) -- the empty block is the empty input's fixed
@@ -166,6 +182,129 @@ __global__ __launch_bounds__(PT) void dmx_eb_pack_kernel(const uint8_t* __restri
     pack_one<true>(b, in, sw, tok_g, codes_g, hdr_g, info, sub_g, max_blocks, flags, out32, res, nullptr, tab);
 }
 
+// ---- K0 and K1 with a history (dmx_encode_batch_dict_async) ----
+__global__ __launch_bounds__(SCT) void dmx_ebd_store_check_kernel(const uint8_t* __restrict__ in, uint32_t sw,
+                                                                  dmx_blkinfo* __restrict__ info, uint32_t* __restrict__ tok_g,
+                                                                  uint32_t* __restrict__ hist_g, uint32_t flags,
+                                                                  const dmx_bblk* __restrict__ tab) {
+    // uni_ok 0, as the single dictionary encode passes it: a block of one repeated byte is parsed by K1,
+    // whose history may hold a longer match than the closed form knows
+    (void)store_check_block<false, true>(in, 0, sw, info, tok_g, hist_g, 0u, flags, nullptr, 0, tab);
+}
+
+struct EbdMatchArgs {
+    EbMatchArgs m;
+    const uint16_t* chs;   // offset so that entry b's own slot, ndicts + b, is the b + 1 match_block adds
+};
+__global__ __launch_bounds__(MT) void dmx_ebd_match_kernel(const EbdMatchArgs a) {
+    match_block<true, 3, false, true>(blockIdx.x, a.m.in, 0, a.m.sw, a.m.max_chain, a.m.mflags, a.m.dist_g, a.chs, a.m.tok_g,
+                                      a.m.hist_g, a.m.info, nullptr, a.m.nfallback, a.m.tab);
+}
+
+// ---- the chains: slot < ndicts sorts that dictionary's last min(len, sw) bytes, slot ndicts + b table
+// entry b.  Void entries, empty blocks and records outside d_dict (no stream that names one has
+// blocks) return at once.
+__global__ __launch_bounds__(MT) void dmx_ebd_chain_kernel(const uint8_t* __restrict__ in, uint32_t sw,
+                                                           const uint8_t* __restrict__ dict, const dmx_ebd d,
+                                                           const dmx_bblk* __restrict__ tab,
+                                                           uint16_t* __restrict__ chs, uint16_t* __restrict__ che,
+                                                           uint32_t* __restrict__ nfallback) {
+    __shared__ MatchLDS L;
+    __shared__ uint64_t tp0[3];
+    const uint32_t slot = blockIdx.x;
+    const uint8_t* src;
+    uint32_t len;
+    if (slot < d.ndicts) {
+        const dmx_bdict r = d.dicts[slot];
+        if (!dmx_ebd_inside(r, d.dict_bytes)) return;
+        len = r.len < sw ? (uint32_t)r.len : sw;
+        src = dict + r.off + (r.len - len);
+    } else {
+        const dmx_bblk e = tab[slot - d.ndicts];
+        if (e.len & DMX_BB_VOID) return;
+        len = e.len & DMX_BB_LEN;
+        src = in + e.off;
+    }
+    chain_block(L, tp0, src, len, slot, chs, che, nfallback, threadIdx.x);
+}
+
+// ---- the history search ----
+struct EbdHistArgs {
+    const uint8_t* in;
+    uint32_t sw;
+    int32_t max_chain;
+    const uint8_t* dict;
+    dmx_ebd d;
+    const uint16_t* chs;
+    const uint16_t* che;
+    uint32_t* hb_g;
+    const dmx_bblk* tab;
+    uint32_t max_blocks;
+    uint32_t resident;   // 1: keep a dictionary's staged history, S and ends while the next entry uses the same slot
+};
+
+// A workgroup walks table entries [w per, (w + 1) per), per = ceil(max_blocks / grid): the ranges
+// follow from the launch alone, so no claim counter.  A first block's history is its dictionary's
+// staged tail and slot, any other block's the sw bytes before it in d_in (block j - 1 of its own
+// stream, which is full) and slot ndicts + b - 1.  Resident: an entry whose history is the
+// dictionary slot staged by the entry before it stages only the block and the crossing bytes behind
+// the history (a dictionary's bytes, S and ends do not change within a call).  With a grid of
+// max_blocks workgroups (the simple form) every workgroup has one entry and stages everything.
+template <int HG>
+__global__ __launch_bounds__(MT) void dmx_ebd_hist_kernel(const EbdHistArgs a) {
+    __shared__ HistLDS L;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t per = (a.max_blocks + gridDim.x - 1) / gridDim.x;
+    const uint64_t b0 = (uint64_t)blockIdx.x * per;
+    const uint32_t b1 = (uint32_t)(b0 + per < a.max_blocks ? b0 + per : a.max_blocks);
+    uint32_t held = 0xFFFFFFFFu, held_hn = 0;   // the dictionary slot whose history L holds (uniform)
+    for (uint32_t b = (uint32_t)(b0 < b1 ? b0 : b1); b < b1; b++) {
+        const dmx_bblk e = a.tab[b];
+        if ((e.len & DMX_BB_VOID) || !(e.len & DMX_BB_LEN)) continue;
+        const uint32_t bn = e.len & DMX_BB_LEN;
+        const uint8_t* cur = a.in + e.off;
+        uint32_t* hb = a.hb_g + (uint64_t)b * DMX_BLK;
+        const uint32_t nvalid = bn > 2 ? bn - 2 : 0;
+        uint32_t hn, slot;
+        const uint8_t* hs;
+        if (e.len & DMX_BB_FIRST) {
+            uint64_t doff = 0;
+            hn = (e.len & DMX_BB_DICT) ? dmx_ebd_history(a.d, e.stream, a.sw, &doff, &slot) : 0u;
+            hs = a.dict + doff;
+        } else {
+            hn = a.sw;
+            hs = cur - a.sw;
+            slot = a.d.ndicts + b - 1;
+        }
+        if (hn < 3) {   // no history entries
+            for (uint32_t k = tid; k < nvalid; k += MT) hb[k] = 0;
+            continue;
+        }
+        __syncthreads();   // (the entry before this one has finished reading L)
+        const bool same = a.resident && (e.len & DMX_BB_FIRST) && slot == held && hn == held_hn;
+        if (same) {   // the chunks from the one that holds the history's last byte to the search's reach
+            const uint32_t c1 = (hn + MAXLEN + 64) / 16 + 1;
+            stage_range(L.data, hn / 16, c1 < DATA_WORDS / 4 ? c1 : DATA_WORDS / 4, hs, hn, cur, bn, tid);
+        } else {
+            stage_bytes(L.data, DATA_WORDS, hs, hn, cur, bn, tid);
+            const uint4* Sg = reinterpret_cast<const uint4*>(a.chs + (uint64_t)slot * DMX_BLK);
+            const uint4* Eg = reinterpret_cast<const uint4*>(a.che + (uint64_t)slot * DMX_NBUCKET);
+            for (uint32_t k = tid; k < (hn - 2 + 7) / 8; k += MT) reinterpret_cast<uint4*>(L.sp)[k] = Sg[k];
+            for (uint32_t k = tid; k < DMX_NBUCKET / 8; k += MT) reinterpret_cast<uint4*>(L.ep)[k] = Eg[k];
+        }
+        if (a.resident) {   // the block and the slack behind it the search may read (bytes past bn never decide)
+            const uint32_t c1 = (bn + 15) / 16 + 6;
+            stage_range(L.cur, 0, c1 < (DMX_BLK / 4 + 80) / 4 ? c1 : (DMX_BLK / 4 + 80) / 4, cur, bn, nullptr, 0, tid);
+        } else {
+            stage_bytes(L.cur, DMX_BLK / 4 + 80, cur, bn, nullptr, 0, tid);
+        }
+        held = (e.len & DMX_BB_FIRST) ? slot : 0xFFFFFFFFu;
+        held_hn = hn;
+        __syncthreads();
+        hist_search<HG>(L, a.chs + (uint64_t)(a.d.ndicts + b) * DMX_BLK, hn, bn, a.max_chain, hb, tid);
+    }
+}
+
 // ---- K3 for a batch: the layout scan of dmx_scan_tile_kernel / dmx_scan_kernel / dmx_scan_apply_kernel /
 // dmx_scan_apply1_kernel with the batch's container rule (their Mono, ScanTile and ScanSums) ----
 
@@ -194,8 +333,9 @@ __device__ __forceinline__ Mono eb_elem(const dmx_blkinfo& bi, uint32_t marks, u
 }
 
 template <bool DB>
-__device__ __forceinline__ void eb_scan_tile(dmx_blkinfo* __restrict__ info, const dmx_bblk* __restrict__ tab,
-                                             uint32_t max_blocks, uint32_t flags, ScanTile* __restrict__ tiles) {
+__global__ __launch_bounds__(SCAN_TILE) void dmx_eb_scan_tile_kernel(dmx_blkinfo* __restrict__ info,
+                                                                    const dmx_bblk* __restrict__ tab, uint32_t max_blocks,
+                                                                    uint32_t flags, ScanTile* __restrict__ tiles) {
     __shared__ Mono wtot[SCAN_TILE / 64];
     __shared__ uint64_t red[SCAN_TILE / 64][4];
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -240,11 +380,6 @@ __device__ __forceinline__ void eb_scan_tile(dmx_blkinfo* __restrict__ info, con
         T.adl_s1 = 0; T.adl_s2 = 0; T.ntok = t0; T.nsto = t1; T.nfix = t2;
         T.kinds = t3;   // (ScanSums::k0: the tile's real blocks, at most SCAN_TILE)
     }
-}
-__global__ __launch_bounds__(SCAN_TILE) void dmx_eb_scan_tile_kernel(dmx_blkinfo* __restrict__ info,
-                                                                    const dmx_bblk* __restrict__ tab, uint32_t max_blocks,
-                                                                    uint32_t flags, ScanTile* __restrict__ tiles) {
-    eb_scan_tile<false>(info, tab, max_blocks, flags, tiles);
 }
 
 // Where the batch ends: every stream ends on a byte boundary, so the composed layout applied to
@@ -294,7 +429,7 @@ __device__ __forceinline__ void eb_publish(dmx_result* __restrict__ res, uint32_
 // every word it shares -- with a neighbour, or with its stream's header and trailer, which the
 // finish kernel ORs in -- is zeroed for K4's ORs.  `write` false (-E_SZ for out_cap): the places
 // only, which the finish kernel reports; no byte of the output is touched.
-template <bool DB = false>
+template <bool DB>
 __device__ __forceinline__ void eb_apply_block(dmx_blkinfo* __restrict__ info, const dmx_bblk* __restrict__ tab, uint32_t b,
                                                uint32_t flags, const Mono& tp, uint32_t* __restrict__ out32, bool write) {
     const uint32_t marks = tab[b].len;
@@ -359,6 +494,7 @@ __global__ __launch_bounds__(ST) void dmx_eb_scan_kernel(ScanTile* __restrict__ 
     if (tid == 0) eb_publish(res, nfallback, rec, head, eb_extent(carry_s, head, out_cap), ScanSums::total(red, ST / 64));
 }
 
+template <bool DB>
 __global__ __launch_bounds__(SCAN_TILE) void dmx_eb_apply_kernel(dmx_blkinfo* __restrict__ info,
                                                                 const dmx_bblk* __restrict__ tab, uint32_t max_blocks,
                                                                 uint32_t flags, const ScanTile* __restrict__ tiles,
@@ -369,10 +505,11 @@ __global__ __launch_bounds__(SCAN_TILE) void dmx_eb_apply_kernel(dmx_blkinfo* __
     const ScanTile& T = tiles[blockIdx.x];
     Mono tp;   // the prefix dmx_eb_scan_kernel left
     tp.s = (uint32_t)T.ps; tp.a = T.pa; tp.c = T.pc;
-    eb_apply_block(info, tab, b, flags, tp, out32, res->status == 0);
+    eb_apply_block<DB>(info, tab, b, flags, tp, out32, res->status == 0);
 }
 
 // up to SA1_MAXT tiles: a workgroup per tile composes the tile aggregates itself (dmx_scan_apply1_kernel)
+template <bool DB>
 __global__ __launch_bounds__(SCAN_TILE) void dmx_eb_scan_apply1_kernel(dmx_blkinfo* __restrict__ info,
                                                                       const dmx_bblk* __restrict__ tab, uint32_t max_blocks,
                                                                       uint32_t flags, uint64_t out_cap,
@@ -417,7 +554,7 @@ __global__ __launch_bounds__(SCAN_TILE) void dmx_eb_scan_apply1_kernel(dmx_blkin
     if (lastwg && tid == 0) eb_publish(res, nfallback, rec, head, ext, ScanSums::total(red, SCAN_TILE / 64));
     __syncthreads();   // (s_pre)
     const uint32_t b = tt * SCAN_TILE + tid;
-    if (b < max_blocks) eb_apply_block(info, tab, b, flags, s_pre, out32, ext.status == 0);
+    if (b < max_blocks) eb_apply_block<DB>(info, tab, b, flags, s_pre, out32, ext.status == 0);
 }
 
 // ---- the streams' CRC-32s (DMX_F_GZIP): dmx_crc_batch_kernel with an entry's geometry read from the
@@ -609,6 +746,18 @@ __global__ __launch_bounds__(64 * EB_FIN_WAVES) void dmx_eb_finish_kernel(const 
                                                                           dmx_eresult* __restrict__ results) {
     eb_finish<false>(st, starts, nstreams, in_bytes, sw, flags, info, head, res, out32, results);
 }
+__global__ __launch_bounds__(64 * EB_FIN_WAVES) void dmx_ebd_finish_kernel(const dmx_estream* __restrict__ st,
+                                                                           const uint64_t* __restrict__ starts,
+                                                                           uint32_t nstreams, uint64_t in_bytes, uint32_t sw,
+                                                                           uint32_t flags, const dmx_blkinfo* __restrict__ info,
+                                                                           const dmx_eb_head* __restrict__ head,
+                                                                           const dmx_result* __restrict__ res,
+                                                                           uint32_t* __restrict__ out32,
+                                                                           dmx_eresult* __restrict__ results, const dmx_ebd d,
+                                                                           const uint32_t* __restrict__ dictid,
+                                                                           const dmx_bblk* __restrict__ tab) {
+    eb_finish<true>(st, starts, nstreams, in_bytes, sw, flags, info, head, res, out32, results, &d, dictid, tab);
+}
 
 // ---- host ----
 static uint32_t eb_sw(int32_t sw) { return (sw <= 0 || sw > DMX_BLK) ? (uint32_t)DMX_BLK : (uint32_t)sw; }
@@ -627,12 +776,32 @@ extern "C" uint64_t dmx_encode_batch_bound(uint64_t total_in, uint32_t nstreams,
     r = dmx_eb_sat(r, 16);
     return r > ~0ull - 3 ? ~0ull & ~3ull : (r + 3) & ~3ull;
 }
+// ... with the DICTID's 4 bytes per stream under DMX_F_FDICT
+extern "C" uint64_t dmx_encode_batch_dict_bound(uint64_t total_in, uint32_t nstreams, int32_t sw, uint32_t flags) {
+    const uint64_t r = dmx_encode_batch_bound(total_in, nstreams, sw, flags & ~DMX_F_GZIP);
+    if (!(flags & DMX_F_FDICT)) return r;
+    const uint64_t x = dmx_eb_sat(r, 4ull * nstreams);
+    return x > ~0ull - 3 ? ~0ull & ~3ull : x;
+}
+
+// the history loop's workgroups: one per compute unit (146 KB of LDS each), at most one per table entry
+extern "C" void dmx_encode_batch_dict_geometry(uint32_t* hist_grid) {
+    if (hist_grid) *hist_grid = crc_device_ncu();
+}
 
 static int eb_flags_ok(uint32_t f) {
     if (f & (DMX_F_DICT | DMX_F_SPLIT | DMX_F_BGZF | DMX_F_FDICT)) return 0;
     if (!(f & DMX_F_FINAL)) return 0;
     if (!(f & DMX_F_HEADER) != !(f & DMX_F_TRAILER)) return 0;
     if ((f & DMX_F_GZIP) && !(f & DMX_F_HEADER)) return 0;
+    return 1;
+}
+static int ebd_flags_ok(uint32_t f) {
+    if (!(f & DMX_F_DICT)) return 0;
+    if (f & (DMX_F_SPLIT | DMX_F_BGZF | DMX_F_GZIP)) return 0;
+    if (!(f & DMX_F_FINAL)) return 0;
+    if (!(f & DMX_F_HEADER) != !(f & DMX_F_TRAILER)) return 0;
+    if ((f & DMX_F_FDICT) && !(f & DMX_F_HEADER)) return 0;
     return 1;
 }
 
@@ -669,23 +838,69 @@ extern "C" int dmx_ctx_reserve_batch(dmx_ctx* c, uint32_t max_blocks, uint32_t m
     return 0;
 }
 
-extern "C" int dmx_encode_batch_async(dmx_ctx* c, const void* d_in, uint64_t in_bytes, const dmx_estream* d_streams,
-                                      uint32_t nstreams, uint32_t max_blocks, const dmx_opts* opts, void* d_out,
-                                      uint64_t out_cap, dmx_eresult* d_results, dmx_ebatch_status* d_status, void* stream) {
+extern "C" int dmx_ctx_reserve_batch_dict(dmx_ctx* c, uint32_t max_blocks, uint32_t max_streams, uint32_t max_dicts,
+                                          int32_t sw, uint32_t flags) {
+    if (!c) return -(int)E_INVAL;
+    if (sw == 0) sw = DMX_BLK;
+    if (sw < 1 || sw > DMX_BLK) return -(int)E_RANGE;
+    if (max_blocks > 0x7FFFFFFFu || max_streams > 0x7FFFFFFFu || max_dicts > 0x7FFFFFFFu) return -(int)E_RANGE;
+    if (flags & (DMX_F_SPLIT | DMX_F_BGZF | DMX_F_GZIP)) return -(int)E_INVAL;
+    const uint64_t slots = (uint64_t)max_blocks + max_dicts;
+    if (max_blocks <= c->cap_blocks && max_blocks <= c->cap_btab && c->bplan && max_streams <= c->cap_bstreams &&
+        c->bdictid && max_dicts <= c->cap_bdicts && slots <= c->cap_chain)
+        return 0;   // nothing to do: no synchronisation
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipDeviceSynchronize());
+    // the chain slots grow with the workspace (ctx_reserve_scratch): a slot per block, one for a single
+    // encode's dictionary, and one per dictionary of a batch
+    c->want |= DMX_F_DICT;
+    if (max_dicts > c->chain_dicts) c->chain_dicts = max_dicts;
+    {
+        const int r = ctx_reserve(c, max_blocks > c->cap_blocks ? max_blocks : c->cap_blocks);
+        if (r) return r;
+    }
+    {
+        const int r = dmx_ctx_reserve_batch(c, max_blocks, max_streams, sw, 0);
+        if (r) return r;
+    }
+    if (max_dicts > c->cap_bdicts || !c->bdictid) {
+        if (c->bdictid) (void)hipFree(c->bdictid);
+        c->bdictid = NULL;
+        c->cap_bdicts = 0;
+        HIPCHK(dmx_malloc(&c->bdictid, ((uint64_t)max_dicts + 1) * sizeof(uint32_t)));
+        c->cap_bdicts = max_dicts;
+    }
+    return 0;
+}
+
+// What only dmx_encode_batch_dict_async has: the dictionaries' bytes and the verdict's records.
+struct EbDicts {
+    const uint8_t* bytes;
+    dmx_ebd d;
+};
+
+// The batch encode, once its caller has looked at the arguments only it has.  dict NULL:
+// dmx_encode_batch_async, whose plan runs with the empty dmx_ebd.
+static int eb_run(dmx_ctx* c, const void* d_in, uint64_t in_bytes, const dmx_estream* d_streams, uint32_t nstreams,
+                  uint32_t max_blocks, const EbDicts* dict, const dmx_opts* opts, void* d_out, uint64_t out_cap,
+                  dmx_eresult* d_results, dmx_ebatch_status* d_status, void* stream) {
     if (!c || !d_out || !d_results || !d_status || (!d_in && in_bytes) || (!d_streams && nstreams)) return -(int)E_INVAL;
     if ((reinterpret_cast<uintptr_t>(d_streams) & 7) || (reinterpret_cast<uintptr_t>(d_results) & 7) ||
         (reinterpret_cast<uintptr_t>(d_status) & 7) || (reinterpret_cast<uintptr_t>(d_out) & 3))
         return -(int)E_INVAL;
     dmx_opts o = {0, 0, DMX_ZLIB, 0, NULL, 0};
     if (opts) o = *opts;
-    if (!eb_flags_ok(o.flags)) return -(int)E_INVAL;
+    if (!(dict ? ebd_flags_ok(o.flags) : eb_flags_ok(o.flags))) return -(int)E_INVAL;
     if (o.sw == 0) o.sw = DMX_BLK;
     if (o.sw < 1 || o.sw > DMX_BLK) return -(int)E_RANGE;
     if (o.max_chain < 0) return -(int)E_RANGE;
     if (o.deep_chain < 0 || o.deep_chain > 255) return -(int)E_RANGE;
-    if (nstreams > 0x7FFFFFFFu || max_blocks > 0x7FFFFFFFu) return -(int)E_RANGE;
+    const uint32_t ndicts = dict ? dict->d.ndicts : 0u;
+    if (nstreams > 0x7FFFFFFFu || max_blocks > 0x7FFFFFFFu || ndicts > 0x7FFFFFFFu) return -(int)E_RANGE;
     if (!c->bplan || !c->btab || max_blocks > c->cap_blocks || max_blocks > c->cap_btab || nstreams > c->cap_bstreams)
         return -(int)E_SZ;
+    if (dict && (!c->bdictid || ndicts > c->cap_bdicts || (uint64_t)max_blocks + ndicts > c->cap_chain)) return -(int)E_SZ;
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     const uint32_t sw = (uint32_t)o.sw, maxb = max_blocks;
@@ -694,64 +909,131 @@ extern "C" int dmx_encode_batch_async(dmx_ctx* c, const void* d_in, uint64_t in_
     dmx_eb_tile* ptiles = (dmx_eb_tile*)(pl + 256);
     uint64_t* starts = (uint64_t*)(pl + eb_off_starts(c->cap_bstreams));
     const uint32_t stiles = (uint32_t)eb_tiles_of(nstreams);
+    const dmx_ebd d = dict ? dict->d : dmx_ebd_none();
+    const dmx_bblk* tab = (const dmx_bblk*)c->btab;
+    // stage times (dmx_ctx_set_timing) of a dictionary batch, with the single encode's boundaries: [0] the
+    // plan, the DICTIDs, the chains, the history search and K0, [1] K1, [2] K2, [3] K3, [4] K4 and the finish
+    hipEvent_t* ev = NULL;
+    if (dict && c->timing && (c->ev_every <= 1 || c->ev_count++ % c->ev_every == 0)) {
+        const int j = (int)(c->ev_next++ % DMX_EV_RING);
+        ctx_collect_set(c, j);
+        ev = c->ev[j];
+        c->ev_used[j] = 1;
+    }
+    auto stamp = [&](int k) { if (ev && ((c->timing >> k) & 1)) (void)hipEventRecord(ev[k], s); };
+    stamp(0);
     // the plan
     if (nstreams)
-        hipLaunchKernelGGL(dmx_eb_count_kernel, dim3(stiles), dim3(EB_WG), 0, s, d_streams, nstreams, in_bytes, sw, ptiles);
+        hipLaunchKernelGGL(dmx_eb_count_kernel, dim3(stiles), dim3(EB_WG), 0, s, d_streams, nstreams, in_bytes, sw, d, ptiles);
     hipLaunchKernelGGL(dmx_eb_plan_scan_kernel, dim3(1), dim3(DMX_EB_STHREADS), 0, s, ptiles, stiles, maxb, head);
     if (nstreams)
-        hipLaunchKernelGGL(dmx_eb_starts_kernel, dim3(stiles), dim3(EB_WG), 0, s, d_streams, nstreams, in_bytes, sw,
+        hipLaunchKernelGGL(dmx_eb_starts_kernel, dim3(stiles), dim3(EB_WG), 0, s, d_streams, nstreams, in_bytes, sw, d,
                            (const dmx_eb_tile*)ptiles, starts, d_results);
+    // the DICTIDs: the Adler-32 of every dictionary (0 for a record outside d_dict, which no header names)
+    if ((o.flags & DMX_F_FDICT) && ndicts && dmx_dict_adler_batch_launch(dict->bytes, d.dict_bytes, d.dicts, ndicts, c->bdictid, s))
+        return -(int)E_DEVICE;
     if (maxb) {
         hipLaunchKernelGGL(dmx_eb_table_kernel, dim3((maxb + EB_WG - 1) / EB_WG), dim3(EB_WG), 0, s, d_streams,
-                           (const uint64_t*)starts, nstreams, (const dmx_eb_head*)head, sw, maxb, c->btab, c->info);
+                           (const uint64_t*)starts, nstreams, (const dmx_eb_head*)head, sw, d, maxb, c->btab, c->info);
         // K0, K1, K2: a workgroup per table entry; void entries return at once
-        if (o.flags & DMX_F_STORE_CHECK)
-            hipLaunchKernelGGL(dmx_eb_store_check_kernel, dim3(maxb), dim3(SCT), 0, s, (const uint8_t*)d_in, sw, c->info,
-                               c->tok, c->hist, o.flags, (const dmx_bblk*)c->btab);
         const uint32_t mfl = ((o.flags & DMX_F_LAZY) ? 1u : 0u) | ((o.flags & DMX_F_EXACT_SORT) ? 2u : 0u) |
                              ((o.flags & DMX_F_STORE_CHECK) ? 4u : 0u) | ((o.flags & DMX_F_DEEP) ? 8u : 0u) |
                              ((uint32_t)o.deep_chain << 16);
-        const EbMatchArgs ma = {(const uint8_t*)d_in, sw, o.max_chain, mfl, c->dist, c->tok, c->hist, c->info, c->nfb,
-                                (const dmx_bblk*)c->btab};
-        if (o.max_chain == 0) hipLaunchKernelGGL(dmx_eb_match_kernel<DMX_NBX>, dim3(maxb), dim3(MT), 0, s, ma);
-        else hipLaunchKernelGGL(dmx_eb_match_kernel<3>, dim3(maxb), dim3(MT), 0, s, ma);
-        // (without DMX_F_FINAL: every header's BFINAL bit is 0, K4 sets it from the table)
+        const EbMatchArgs ma = {(const uint8_t*)d_in, sw, o.max_chain, mfl, c->dist, c->tok, c->hist, c->info, c->nfb, tab};
+        if (dict) {   // the chains of the dictionaries and of every table entry, then the history search
+            hipLaunchKernelGGL(dmx_ebd_chain_kernel, dim3(ndicts + maxb), dim3(MT), 0, s, (const uint8_t*)d_in, sw,
+                               dict->bytes, d, tab, c->chs, c->che, c->nfb);
+            const uint32_t resident = c->hk_bdict_simple ? 0u : 1u;
+            const EbdHistArgs ha = {(const uint8_t*)d_in, sw, o.max_chain, dict->bytes, d, c->chs, c->che, c->tok, tab, maxb,
+                                    resident};
+            hipLaunchKernelGGL((o.max_chain >= 1 && o.max_chain <= 6) ? dmx_ebd_hist_kernel<6>
+                               : o.max_chain == 7 ? dmx_ebd_hist_kernel<7> : dmx_ebd_hist_kernel<8>,
+                               dim3(resident ? (maxb < c->ncu ? maxb : c->ncu) : maxb), dim3(MT), 0, s, ha);
+        }
+        if (o.flags & DMX_F_STORE_CHECK)
+            hipLaunchKernelGGL(dict ? dmx_ebd_store_check_kernel : dmx_eb_store_check_kernel, dim3(maxb), dim3(SCT), 0, s,
+                               (const uint8_t*)d_in, sw, c->info, c->tok, c->hist, o.flags, tab);
+        stamp(1);
+        if (dict) {
+            // (match_block reads its own chains at slot b + 1: ndicts - 1 slots further, that is ndicts + b)
+            const uint16_t* chs1 = reinterpret_cast<const uint16_t*>(reinterpret_cast<uintptr_t>(c->chs) +
+                                                                      ((uintptr_t)ndicts - 1) * DMX_BLK * sizeof(uint16_t));
+            const EbdMatchArgs dma = {ma, chs1};
+            hipLaunchKernelGGL(dmx_ebd_match_kernel, dim3(maxb), dim3(MT), 0, s, dma);
+        } else if (o.max_chain == 0) {
+            hipLaunchKernelGGL(dmx_eb_match_kernel<DMX_NBX>, dim3(maxb), dim3(MT), 0, s, ma);
+        } else {
+            hipLaunchKernelGGL(dmx_eb_match_kernel<3>, dim3(maxb), dim3(MT), 0, s, ma);
+        }
+        stamp(2);
+        // (without DMX_F_FINAL: every header's BFINAL bit is 0, K4 sets it from the table; K2 and K4 frame
+        // nothing in a batch, so the dictionary flags, which only a dictionary batch has, stop here too)
         hipLaunchKernelGGL(dmx_huff_kernel, dim3(maxb), dim3(64), 0, s, c->hist, c->info, c->codes, c->hdr, c->sub, maxb,
-                           o.flags & ~DMX_F_FINAL, (const uint32_t*)NULL, (const uint32_t*)NULL, (const uint16_t*)NULL);
+                           o.flags & ~(DMX_F_FINAL | DMX_F_FDICT), (const uint32_t*)NULL, (const uint32_t*)NULL,
+                           (const uint16_t*)NULL);
+        stamp(3);
+    } else {
+        for (int k = 1; k <= 3; k++) stamp(k);
     }
     // K3
     const uint32_t ntile = (maxb + SCAN_TILE - 1) / SCAN_TILE;
     if (maxb)
-        hipLaunchKernelGGL(dmx_eb_scan_tile_kernel, dim3(ntile), dim3(SCAN_TILE), 0, s, c->info, (const dmx_bblk*)c->btab,
-                           maxb, o.flags, c->tiles);
+        hipLaunchKernelGGL(dict ? dmx_eb_scan_tile_kernel<true> : dmx_eb_scan_tile_kernel<false>, dim3(ntile), dim3(SCAN_TILE),
+                           0, s, c->info, tab, maxb, o.flags, c->tiles);
     if (maxb && ntile <= SA1_MAXT && !c->hk_scan3) {
-        hipLaunchKernelGGL(dmx_eb_scan_apply1_kernel, dim3(ntile), dim3(SCAN_TILE), 0, s, c->info, (const dmx_bblk*)c->btab,
-                           maxb, o.flags, out_cap, (const ScanTile*)c->tiles, (uint32_t*)d_out, c->res, c->nfb,
-                           (const dmx_eb_head*)head, d_status);
+        hipLaunchKernelGGL(dict ? dmx_eb_scan_apply1_kernel<true> : dmx_eb_scan_apply1_kernel<false>, dim3(ntile),
+                           dim3(SCAN_TILE), 0, s, c->info, tab, maxb, o.flags, out_cap, (const ScanTile*)c->tiles,
+                           (uint32_t*)d_out, c->res, c->nfb, (const dmx_eb_head*)head, d_status);
     } else {
         hipLaunchKernelGGL(dmx_eb_scan_kernel, dim3(1), dim3(ST), 0, s, c->tiles, maxb, out_cap, c->res, c->nfb,
                            (const dmx_eb_head*)head, d_status);
         if (maxb)
-            hipLaunchKernelGGL(dmx_eb_apply_kernel, dim3(ntile), dim3(SCAN_TILE), 0, s, c->info, (const dmx_bblk*)c->btab,
-                               maxb, o.flags, (const ScanTile*)c->tiles, (uint32_t*)d_out, (const dmx_result*)c->res);
+            hipLaunchKernelGGL(dict ? dmx_eb_apply_kernel<true> : dmx_eb_apply_kernel<false>, dim3(ntile), dim3(SCAN_TILE), 0,
+                               s, c->info, tab, maxb, o.flags, (const ScanTile*)c->tiles, (uint32_t*)d_out,
+                               (const dmx_result*)c->res);
     }
+    stamp(4);
     if (maxb)
         hipLaunchKernelGGL(dmx_eb_pack_kernel, dim3(maxb), dim3(PT), 0, s, (const uint8_t*)d_in, sw, c->tok, c->codes,
-                           c->hdr, c->info, c->sub, maxb, o.flags, (uint32_t*)d_out, c->res, (const dmx_bblk*)c->btab);
+                           c->hdr, c->info, c->sub, maxb, o.flags & ~(DMX_F_FDICT | DMX_F_DICT), (uint32_t*)d_out, c->res, tab);
     if (nstreams) {
-        if (o.flags & DMX_F_GZIP) {
+        const dim3 fgrid((nstreams + EB_FIN_WAVES - 1) / EB_FIN_WAVES), fwg(64 * EB_FIN_WAVES);
+        if (o.flags & DMX_F_GZIP) {   // (the plain batch only: ebd_flags_ok refuses gzip)
             const uint32_t gmax = 3 * crc_device_ncu();   // 3 workgroups of 52 KiB LDS per CU
             hipLaunchKernelGGL(dmx_eb_crc_kernel, dim3(nstreams < gmax ? nstreams : gmax), dim3(CRC_T), 0, s,
                                (const uint8_t*)d_in, in_bytes, d_streams, nstreams, d_results);
         }
-        hipLaunchKernelGGL(dmx_eb_finish_kernel, dim3((nstreams + EB_FIN_WAVES - 1) / EB_FIN_WAVES), dim3(64 * EB_FIN_WAVES),
-                           0, s, d_streams, (const uint64_t*)starts, nstreams, in_bytes, sw, o.flags,
-                           (const dmx_blkinfo*)c->info, (const dmx_eb_head*)head, (const dmx_result*)c->res,
-                           (uint32_t*)d_out, d_results);
+        if (dict)
+            hipLaunchKernelGGL(dmx_ebd_finish_kernel, fgrid, fwg, 0, s, d_streams, (const uint64_t*)starts, nstreams, in_bytes,
+                               sw, o.flags, (const dmx_blkinfo*)c->info, (const dmx_eb_head*)head, (const dmx_result*)c->res,
+                               (uint32_t*)d_out, d_results, d, (const uint32_t*)c->bdictid, tab);
+        else
+            hipLaunchKernelGGL(dmx_eb_finish_kernel, fgrid, fwg, 0, s, d_streams, (const uint64_t*)starts, nstreams, in_bytes,
+                               sw, o.flags, (const dmx_blkinfo*)c->info, (const dmx_eb_head*)head, (const dmx_result*)c->res,
+                               (uint32_t*)d_out, d_results);
     }
+    stamp(5);
     HIPCHK(fault_hit(2) ? hipErrorLaunchFailure : hipGetLastError());
     c->last_nblk = 0;   // (the per-block introspection addresses blocks by b * sw)
     c->last_sw = sw;
     c->last_batch = 1;
     return 0;
+}
+
+extern "C" int dmx_encode_batch_async(dmx_ctx* c, const void* d_in, uint64_t in_bytes, const dmx_estream* d_streams,
+                                      uint32_t nstreams, uint32_t max_blocks, const dmx_opts* opts, void* d_out,
+                                      uint64_t out_cap, dmx_eresult* d_results, dmx_ebatch_status* d_status, void* stream) {
+    return eb_run(c, d_in, in_bytes, d_streams, nstreams, max_blocks, NULL, opts, d_out, out_cap, d_results, d_status, stream);
+}
+
+extern "C" int dmx_encode_batch_dict_async(dmx_ctx* c, const void* d_in, uint64_t in_bytes, const dmx_estream* d_streams,
+                                           uint32_t nstreams, uint32_t max_blocks, const void* d_dict, uint64_t dict_bytes,
+                                           const dmx_bdict* d_dicts, uint32_t ndicts, const uint32_t* d_dict_of,
+                                           const dmx_opts* opts, void* d_out, uint64_t out_cap, dmx_eresult* d_results,
+                                           dmx_ebatch_status* d_status, void* stream) {
+    if ((!d_dicts && ndicts) || (!d_dict && dict_bytes)) return -(int)E_INVAL;
+    if ((reinterpret_cast<uintptr_t>(d_dicts) & 7) || (reinterpret_cast<uintptr_t>(d_dict_of) & 3)) return -(int)E_INVAL;
+    const uint32_t fdict = (opts && (opts->flags & DMX_F_FDICT)) ? 1u : 0u;
+    const EbDicts dict = {(const uint8_t*)d_dict, {d_dicts, d_dict_of, dict_bytes, ndicts, fdict}};
+    return eb_run(c, d_in, in_bytes, d_streams, nstreams, max_blocks, &dict, opts, d_out, out_cap, d_results, d_status, stream);
 }

@@ -1899,12 +1899,12 @@ __device__ __forceinline__ uint32_t gram_pass(MatchLDS& L, uint32_t nv, uint32_t
 // ------------------------------------------------------------------------------------
 #define TB8(W, i) (reinterpret_cast<const uint8_t*>(W)[i])
 
-// Stage bytes src[0, len) at LDS word array W (16-byte chunks, zero padded to nwords).
-__device__ __forceinline__ void stage_bytes(uint32_t* W, uint32_t nwords, const uint8_t* src, uint32_t len,
+// Stage the 16-byte chunks [c0, c1) of LDS word array W: bytes [0, len) from src, then
+// [len, len + len2) from src2, then zeros.
+__device__ __forceinline__ void stage_range(uint32_t* W, uint32_t c0, uint32_t c1, const uint8_t* src, uint32_t len,
                                             const uint8_t* src2, uint32_t len2, uint32_t tid) {
-    // bytes [0, len) from src, then [len, len + len2) from src2, then zeros
     const bool al = ((reinterpret_cast<uintptr_t>(src) & 15) == 0);
-    for (uint32_t k = tid; k < nwords / 4; k += MT) {
+    for (uint32_t k = c0 + tid; k < c1; k += MT) {
         const uint32_t p = k << 4;
         uint4 v;
         if (al && p + 16 <= len) {
@@ -1921,6 +1921,11 @@ __device__ __forceinline__ void stage_bytes(uint32_t* W, uint32_t nwords, const 
         *reinterpret_cast<uint4*>(&W[k << 2]) = v;
     }
 }
+// ... all of W, zero padded to nwords
+__device__ __forceinline__ void stage_bytes(uint32_t* W, uint32_t nwords, const uint8_t* src, uint32_t len,
+                                            const uint8_t* src2, uint32_t len2, uint32_t tid) {
+    stage_range(W, 0, nwords / 4, src, len, src2, len2, tid);
+}
 
 // History of block b: its bytes and length (0 = none).
 __device__ __forceinline__ const uint8_t* hist_of(const uint8_t* in, uint32_t sw, uint32_t b, const uint8_t* pre,
@@ -1930,23 +1935,11 @@ __device__ __forceinline__ const uint8_t* hist_of(const uint8_t* in, uint32_t sw
     return hn ? pre + (npre - hn) : nullptr;
 }
 
-__global__ __launch_bounds__(MT) void dmx_chain_kernel(const uint8_t* __restrict__ in, uint64_t n, uint32_t sw,
-                                                       const uint8_t* __restrict__ pre, uint32_t npre,
-                                                       uint16_t* __restrict__ chs, uint16_t* __restrict__ che,
-                                                       uint32_t* __restrict__ nfallback) {
-    __shared__ MatchLDS L;
-    __shared__ uint64_t tp0[3];
-    const uint32_t tid = threadIdx.x;
-    const uint32_t slot = blockIdx.x;
-    const uint8_t* src;
-    uint32_t len;
-    if (slot == 0) {
-        src = hist_of(in, sw, 0, pre, npre, len);
-    } else {
-        const uint64_t off = (uint64_t)(slot - 1) * sw;
-        len = (uint32_t)((n - off) < sw ? (n - off) : sw);
-        src = in + off;
-    }
+// The chains of one workgroup's bytes src[0, len) into chain slot `slot`: S and the bucket ends.
+// The caller (dmx_chain_kernel, the batch's dmx_ebd_chain_kernel) finds src, len and slot.
+__device__ __forceinline__ void chain_block(MatchLDS& L, uint64_t* tp0, const uint8_t* src, uint32_t len, uint32_t slot,
+                                            uint16_t* __restrict__ chs, uint16_t* __restrict__ che,
+                                            uint32_t* __restrict__ nfallback, uint32_t tid) {
     if (len < 3) return;   // no entries (slot 0 without a dict)
     stage_bytes(L.data, DATA_WORDS, src, len, nullptr, 0, tid);
     const uint32_t nv = len - 2;
@@ -1992,6 +1985,25 @@ __global__ __launch_bounds__(MT) void dmx_chain_kernel(const uint8_t* __restrict
         reinterpret_cast<uint4*>(S)[k] = reinterpret_cast<const uint4*>(L.sorted)[k];
     for (uint32_t k = tid; k < DMX_NBUCKET / 8; k += MT)
         reinterpret_cast<uint4*>(E)[k] = reinterpret_cast<const uint4*>(L.bstart)[k];
+}
+
+__global__ __launch_bounds__(MT) void dmx_chain_kernel(const uint8_t* __restrict__ in, uint64_t n, uint32_t sw,
+                                                       const uint8_t* __restrict__ pre, uint32_t npre,
+                                                       uint16_t* __restrict__ chs, uint16_t* __restrict__ che,
+                                                       uint32_t* __restrict__ nfallback) {
+    __shared__ MatchLDS L;
+    __shared__ uint64_t tp0[3];
+    const uint32_t slot = blockIdx.x;
+    const uint8_t* src;
+    uint32_t len;
+    if (slot == 0) {
+        src = hist_of(in, sw, 0, pre, npre, len);
+    } else {
+        const uint64_t off = (uint64_t)(slot - 1) * sw;
+        len = (uint32_t)((n - off) < sw ? (n - off) : sw);
+        src = in + off;
+    }
+    chain_block(L, tp0, src, len, slot, chs, che, nfallback, threadIdx.x);
 }
 
 // 146 KB, one workgroup per CU: the history, the block and the history's chains (S and the
@@ -2085,39 +2097,14 @@ __device__ __forceinline__ void hist_flush(const HistLDS& L, uint32_t wave, uint
     __builtin_amdgcn_wave_barrier();
 }
 
-// HG = history candidates per group: 6 for K <= 6, 7 for K = 7 (the bench default), 8 otherwise
-// (K > 8 in groups of 8).
+// The search of one staged block: for every entry k of the block's S (Sc: its bn - 2 entries in
+// bucket order), the longest match against the history staged in L (hn bytes, its S and bucket
+// ends), into hb[k].  HG = history candidates per group: 6 for K <= 6, 7 for K = 7 (the bench
+// default), 8 otherwise (K > 8 in groups of 8).
 template <int HG>
-__global__ __launch_bounds__(MT) void dmx_hist_kernel_t(const uint8_t* __restrict__ in, uint64_t n, uint32_t sw,
-                                                      int32_t max_chain, const uint8_t* __restrict__ pre, uint32_t npre,
-                                                      const uint16_t* __restrict__ chs, const uint16_t* __restrict__ che,
-                                                      uint32_t* __restrict__ hb_g, uint64_t* __restrict__ dbg) {
-    __shared__ HistLDS L;
-    const uint32_t tid = threadIdx.x;
-    const uint32_t b = blockIdx.x;
-    const uint64_t off = (uint64_t)b * sw;
-    const uint32_t bn = (uint32_t)((n - off) < sw ? (n - off) : sw);
-    const uint8_t* cur = in + off;
-    uint32_t hn;
-    const uint8_t* hs = hist_of(in, sw, b, pre, npre, hn);
-    uint32_t* hb = hb_g + (uint64_t)b * DMX_BLK;
+__device__ __forceinline__ void hist_search(HistLDS& L, const uint16_t* __restrict__ Sc, uint32_t hn, uint32_t bn,
+                                            int32_t max_chain, uint32_t* __restrict__ hb, uint32_t tid) {
     const uint32_t nvalid = bn > 2 ? bn - 2 : 0;
-    if (hn < 3) {   // no history entries
-        for (uint32_t k = tid; k < nvalid; k += MT) hb[k] = 0;
-        return;
-    }
-    const uint64_t tbeg = dbg ? __builtin_amdgcn_s_memtime() : 0;
-    stage_bytes(L.data, DATA_WORDS, hs, hn, cur, bn, tid);
-    stage_bytes(L.cur, DMX_BLK / 4 + 80, cur, bn, nullptr, 0, tid);
-    {   // the history's chains: S (hn - 2 entries, 8 per 16-byte load) and the bucket ends
-        const uint4* Sg = reinterpret_cast<const uint4*>(chs + (uint64_t)b * DMX_BLK);
-        const uint4* Eg = reinterpret_cast<const uint4*>(che + (uint64_t)b * DMX_NBUCKET);
-        for (uint32_t k = tid; k < (hn - 2 + 7) / 8; k += MT) reinterpret_cast<uint4*>(L.sp)[k] = Sg[k];
-        for (uint32_t k = tid; k < DMX_NBUCKET / 8; k += MT) reinterpret_cast<uint4*>(L.ep)[k] = Eg[k];
-    }
-    __syncthreads();
-    const uint64_t ts0 = dbg ? __builtin_amdgcn_s_memtime() : 0;
-    const uint16_t* Sc = chs + (uint64_t)(b + 1) * DMX_BLK;   // the block's entries in bucket order
     const uint16_t* Ep = L.ep;                                // the history's bucket ends (LDS)
     const uint32_t K = max_chain > 0 ? (uint32_t)max_chain : 0xFFFFFFFFu;
     const uint32_t lane = tid & 63, wave = wave_of(tid);
@@ -2171,6 +2158,38 @@ __global__ __launch_bounds__(MT) void dmx_hist_kernel_t(const uint8_t* __restric
         qn += np;
     }
     if (qn) hist_flush(L, wave, qn, lane, hn, bn, hb);
+}
+
+template <int HG>
+__global__ __launch_bounds__(MT) void dmx_hist_kernel_t(const uint8_t* __restrict__ in, uint64_t n, uint32_t sw,
+                                                      int32_t max_chain, const uint8_t* __restrict__ pre, uint32_t npre,
+                                                      const uint16_t* __restrict__ chs, const uint16_t* __restrict__ che,
+                                                      uint32_t* __restrict__ hb_g, uint64_t* __restrict__ dbg) {
+    __shared__ HistLDS L;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t b = blockIdx.x;
+    const uint64_t off = (uint64_t)b * sw;
+    const uint32_t bn = (uint32_t)((n - off) < sw ? (n - off) : sw);
+    const uint8_t* cur = in + off;
+    uint32_t hn;
+    const uint8_t* hs = hist_of(in, sw, b, pre, npre, hn);
+    uint32_t* hb = hb_g + (uint64_t)b * DMX_BLK;
+    if (hn < 3) {   // no history entries
+        for (uint32_t k = tid; k + 2 < bn; k += MT) hb[k] = 0;   // (bn - 2 entries)
+        return;
+    }
+    const uint64_t tbeg = dbg ? __builtin_amdgcn_s_memtime() : 0;
+    stage_bytes(L.data, DATA_WORDS, hs, hn, cur, bn, tid);
+    stage_bytes(L.cur, DMX_BLK / 4 + 80, cur, bn, nullptr, 0, tid);
+    {   // the history's chains: S (hn - 2 entries, 8 per 16-byte load) and the bucket ends
+        const uint4* Sg = reinterpret_cast<const uint4*>(chs + (uint64_t)b * DMX_BLK);
+        const uint4* Eg = reinterpret_cast<const uint4*>(che + (uint64_t)b * DMX_NBUCKET);
+        for (uint32_t k = tid; k < (hn - 2 + 7) / 8; k += MT) reinterpret_cast<uint4*>(L.sp)[k] = Sg[k];
+        for (uint32_t k = tid; k < DMX_NBUCKET / 8; k += MT) reinterpret_cast<uint4*>(L.ep)[k] = Eg[k];
+    }
+    __syncthreads();
+    const uint64_t ts0 = dbg ? __builtin_amdgcn_s_memtime() : 0;
+    hist_search<HG>(L, chs + (uint64_t)(b + 1) * DMX_BLK, hn, bn, max_chain, hb, tid);
     if (dbg) {   // stamps 12..15: staged, searched
         __syncthreads();
         if (tid == 0) {
@@ -6057,9 +6076,8 @@ extern "C" int dmx_last_subblock(dmx_ctx* c, uint32_t blk, uint32_t sub, uint32_
     return (int)bi.nsub;
 }
 
-// Batches of independent buffers into independent streams (dmx_encode_batch_async): the plan, the
-// batch instantiations of K0 / K1 / K4, K3's batch layout and the per-stream finish have a file of
-// their own, compiled into this translation unit as dmx_crc.hip is.
+// Batches of independent buffers into independent streams (dmx_encode_batch_async, and against preset
+// dictionaries dmx_encode_batch_dict_async): the plan, the batch instantiations of K0 / K1 / K4, K3's
+// batch layout and the per-stream finish have a file of their own, compiled into this translation
+// unit as dmx_crc.hip is.
 #include "dmx_encode_batch.hip"
-// ... and against preset dictionaries (dmx_encode_batch_dict_async)
-#include "dmx_encode_batch_dict.hip"

@@ -781,7 +781,7 @@ int dmx_encode_batch_async(dmx_ctx* ctx, const void* d_in, uint64_t in_bytes,
                            const dmx_estream* d_streams, uint32_t nstreams, uint32_t max_blocks,
                            const dmx_opts* opts, void* d_out, uint64_t out_cap,
                            dmx_eresult* d_results, dmx_ebatch_status* d_status, void* stream);
-/* Batches against preset dictionaries (csrc/dmx_encode_batch_dict.hip): the encode's
+/* Batches against preset dictionaries (csrc/dmx_encode_batch.hip): the encode's
  * counterpart of dmx_inflate_batch_dict_async, beside dmx_encode_batch_async as that call is beside
  * dmx_inflate_batch_async.  The dictionaries are described as there: dictionary j is
  * d_dict[d_dicts[j].off, + d_dicts[j].len), any length and alignment, device memory; stream k uses

@@ -35,8 +35,8 @@ def test_exports_and_declarations():
         assert name in D.__all__ and hasattr(D, name), name
     assert hasattr(D.Encoder, "reserve_batch_dict") and D.Encoder.HOOKS["bdict_simple"] == 4
     blob = open(D.LIB_PATH, "rb").read()
-    for k in (b"dmx_ebd_table_kernel", b"dmx_ebd_chain_kernel", b"dmx_ebd_hist_kernel", b"dmx_ebd_match_kernel",
-              b"dmx_ebd_store_check_kernel", b"dmx_ebd_scan_apply1_kernel", b"dmx_ebd_finish_kernel"):
+    for k in (b"dmx_eb_table_kernel", b"dmx_ebd_chain_kernel", b"dmx_ebd_hist_kernel", b"dmx_ebd_match_kernel",
+              b"dmx_ebd_store_check_kernel", b"dmx_eb_scan_apply1_kernel", b"dmx_ebd_finish_kernel"):
         assert k in blob, k
 
 

@@ -369,6 +369,66 @@ def test_void_entries_capacities_and_bad_streams(enc):
     assert z11 == _single(tb[48:1148], _pre(1025, 3), o2) == _oracle(tb[48:1148], _pre(1025, 3), o2)
 
 
+SCAN_TILE = 256   # table entries per workgroup of K3 (csrc: SCAN_TILE)
+
+
+def test_scan3_hook_across_tiles(enc):
+    """K3's two launch shapes (one launch per tile that composes the aggregates itself; the scan3 hook's
+    scan by one workgroup + apply) give the same bytes on a dictionary batch whose 525 blocks span
+    three scan tiles: 300 buffers of 0 to 2 500 bytes at sw 1024 that name dictionary 0, dictionary 1
+    or none in turn (48-bit and 16-bit headers in one scan), one of them empty, one refused; stream 148
+    begins a tile and stream 147 ends the tile before it.  With max_blocks exact and with a whole void
+    tile behind the real blocks, and under -E_SZ for out_cap."""
+    n, bad, empty = 300, 101, 60
+    lens = [(k * 977 + 311) % 2501 for k in range(n)]
+    lens[empty] = 0
+    bufs = [_buf(m, 100 + k) for k, m in enumerate(lens)]
+    dicts = [_pre(1024, 12), _pre(300, 13)]
+    of = [(0, 1, NODICT)[k % 3] for k in range(n)]
+    t, desc = _lay(bufs, 6)
+    dict_t, ddesc = _lay(dicts, 9)
+    desc[bad] = [t.numel() + 5, 10]   # in_off beyond the input
+    # the plan, which is deterministic: a refused stream has no blocks, every other max(1, ceil(len / sw))
+    nb = [0 if k == bad else max(1, -(-m // 1024)) for k, m in enumerate(lens)]
+    starts = np.concatenate(([0], np.cumsum(nb)))
+    exact = int(starts[-1])
+    assert exact > 2 * SCAN_TILE and min(lens) == 0 and max(lens) <= 2500
+    firsts = [k for k in range(1, n) if nb[k] and starts[k] % SCAN_TILE == 0]
+    lasts = [k for k in range(n) if nb[k] and starts[k + 1] % SCAN_TILE == 0]
+    assert firsts == [148] and lasts == [147] and of[148] == 1 and of[147] == 0 and of[empty] == 0
+    assert {of[k] for k in range(n) if k != bad} == {0, 1, NODICT}
+    opts = D.Opts(1024, 7, Z | DICT | FD | D.DMX_F_LAZY, 0)
+    runs, short = {}, {}
+    try:
+        for scan3 in (0, 1):
+            enc.set_hook("scan3", scan3)
+            for mb in (exact, exact + SCAN_TILE):
+                outb, results, rec = _batch(enc, t, desc, dict_t, ddesc, of, opts, max_blocks=mb)
+                runs[scan3, mb] = (outb.tobytes(), results.tobytes(), bytes(rec))
+                assert rec.status == 0 and rec.nblocks == exact and rec.nfailed == 1 and rec.first_bad == bad
+                a4 = (rec.out_len + 3) & ~3
+                sb, sres, srec = _batch(enc, t, desc, dict_t, ddesc, of, opts, max_blocks=mb, out_cap=a4 - 4)
+                assert srec.status == -E["E_SZ"] and srec.out_len == rec.out_len and (sb == SENT).all(), (scan3, mb)
+                short[scan3, mb] = (sres.tobytes(), bytes(srec))
+    finally:
+        enc.set_hook("scan3", 0)
+    assert len(set(runs.values())) == 1 and len(set(short.values())) == 1
+    outb, results, rec = _batch(enc, t, desc, dict_t, ddesc, of, opts, max_blocks=exact)
+    assert (outb.tobytes(), results.tobytes(), bytes(rec)) == runs[0, exact]
+    pos = 0
+    for k, data in enumerate(bufs):
+        r = results[k]
+        assert int(r["out_off"]) == pos, k
+        if k == bad:
+            assert (r["status"], r["out_len"], r["nblocks"]) == (-E["E_RANGE"], 0, 0)
+            continue
+        assert r["status"] == 0 and r["nblocks"] == nb[k], k
+        got = outb[pos:pos + int(r["out_len"])].tobytes()
+        assert got == _single(data, None if of[k] == NODICT else dicts[of[k]], opts), (k, len(data))
+        pos += int(r["out_len"])
+    assert rec.out_len == pos and (outb[(pos + 3) & ~3:] == SENT).all()
+
+
 def test_graph_replays_with_rewritten_dictionary(enc):
     """one call captured and replayed twice with the dictionary bytes rewritten between the replays:
     the second output names (DICTID) and uses the new dictionary"""
