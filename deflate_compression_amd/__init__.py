@@ -17,6 +17,8 @@ include/dmx.h).  This module is a thin ctypes layer:
     inflate_batch(streams)                                many independent zlib / gzip / raw DEFLATE streams, side by side
                                                           (zdict=: preset dictionaries, zlib's FDICT / inflateSetDictionary)
     inflate_parallel_plan_host(z)                         ONE zlib / gzip / raw stream cut at true block starts (host)
+    zindex_build(z) -> ZIndex                             ONE such stream indexed once on the host: seek points with windows
+    inflate_indexed(zt, ix) / zindex_pread(zt, ix, off, n)  ... then decoded a wave per point, or only the points a range touches
     compress_batch(bufs)                                  many independent buffers into as many streams, in one chain of launches
     Encoder                                               device-resident encodes
 
@@ -41,6 +43,8 @@ __all__ = [
     "compress_batch", "compress_batch_async", "encode_batch_blocks", "EStream", "EResult", "EBatchStatus", "ERESULT_DTYPE",
     "compress_batch_dict_async",
     "inflate_parallel_plan_host", "PChunk", "ParStatus", "PCHUNK_DTYPE",
+    "ZIndex", "ZIndexStatus", "zindex_build", "inflate_points_async", "inflate_indexed", "zindex_read_ranges", "zindex_pread",
+    "DMX_ZINDEX_WINDOW", "DMX_ZINDEX_DEF_SPAN", "DMX_ZINDEX_MAX_SPAN",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -66,6 +70,9 @@ DMX_RANGES_VIRTUAL = 1
 DMX_BATCH_AUTO, DMX_BATCH_ZLIB, DMX_BATCH_GZIP, DMX_BATCH_RAW = 0, 1, 2, 3
 DMX_BATCH_MEASURE = 16
 DMX_BATCH_NODICT = 0xFFFFFFFF
+DMX_ZINDEX_WINDOW = 32768
+DMX_ZINDEX_DEF_SPAN = 256 << 10
+DMX_ZINDEX_MAX_SPAN = 1 << 30
 _M = 1 << 24
 # src/include/global_errors.h:24-35 and src/include/deflate_errors.h:9-22
 E = {
@@ -152,6 +159,13 @@ class ParStatus(ctypes.Structure):
                 ("in_used", ctypes.c_uint64), ("check", ctypes.c_uint32), ("nchunks", ctypes.c_uint32),
                 ("ncand", ctypes.c_uint32), ("nlive", ctypes.c_uint32), ("ndead", ctypes.c_uint32),
                 ("gave_up", ctypes.c_uint32), ("work_len", ctypes.c_uint64)]
+
+
+class ZIndexStatus(ctypes.Structure):
+    """dmx_zindex_status: the 40-byte record of dmx_zindex_build_host"""
+    _fields_ = [("status", ctypes.c_int32), ("format", ctypes.c_uint32), ("out_len", ctypes.c_uint64),
+                ("in_used", ctypes.c_uint64), ("check", ctypes.c_uint32), ("npoints", ctypes.c_uint32),
+                ("span", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
 # numpy's view of dmx_pchunk records
@@ -246,6 +260,10 @@ def lib() -> ctypes.CDLL:
         "dmx_inflate_dict_host": ([vp, u64, u32, vp, u64, ctypes.POINTER(vp), ctypes.POINTER(u64), ctypes.POINTER(u64)],
                                   ctypes.c_int),
         "dmx_inflate_parallel_plan_host": ([vp, u64, u32, u32, vp, u32, ctypes.POINTER(ParStatus)], ctypes.c_int),
+        "dmx_zindex_build_host": ([vp, u64, u32, u32, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
+                                   ctypes.POINTER(ZIndexStatus)], ctypes.c_int),
+        "dmx_inflate_points_work": ([u32], u64),
+        "dmx_inflate_points_async": ([vp, u64, vp, vp, vp, u32, vp, vp, u32, vp, u64, vp, vp, u64, vp, vp], ctypes.c_int),
         "dmx_encode_batch_blocks": ([u64, u32, i32], u32),
         "dmx_encode_batch_bound": ([u64, u32, i32, u32], u64),
         "dmx_ctx_reserve_batch": ([vp, u32, u32, i32, u32], ctypes.c_int),
@@ -922,6 +940,219 @@ def inflate_parallel_plan_host(z, fmt: str = "auto", chunk_bytes: int | None = N
     del zk
     _check(r, "dmx_inflate_parallel_plan_host")
     return chunks, _par_info(rec)
+
+
+class ZIndex:
+    """The seek-point index of one zlib stream, gzip member or raw DEFLATE stream (zindex_build;
+    dmx_zindex_build_host): points, a numpy array of PCHUNK_DTYPE records (bit, end_bit, out_off,
+    out_len); adlers, the uint32 Adler-32 of every point's bytes; windows, a uint8 array of
+    (npoints, 32768) with the output in front of every point right-aligned in its slot; and format
+    (1 zlib, 2 gzip, 3 raw), out_len, in_used (through the trailer), check (the stored Adler-32 /
+    CRC-32) and span of the stream.  cuda(device) makes the device copies once per device."""
+
+    def __init__(self, points, adlers, windows, format: int, out_len: int, in_used: int, check: int, span: int):
+        import numpy as np
+        self.points = np.ascontiguousarray(points, dtype=PCHUNK_DTYPE)
+        self.adlers = np.ascontiguousarray(adlers, dtype=np.uint32)
+        self.windows = np.ascontiguousarray(windows, dtype=np.uint8).reshape(-1, DMX_ZINDEX_WINDOW)
+        if not (self.points.shape[0] == self.adlers.shape[0] == self.windows.shape[0]):
+            raise ValueError("points, adlers and windows have one entry per point")
+        self.format, self.out_len, self.in_used, self.check, self.span = (int(format), int(out_len), int(in_used),
+                                                                          int(check), int(span))
+        self._dev = {}
+
+    @property
+    def npoints(self) -> int:
+        return int(self.points.shape[0])
+
+    @property
+    def nbytes(self) -> int:
+        return int(self.points.nbytes + self.adlers.nbytes + self.windows.nbytes)
+
+    def cuda(self, device=None):
+        """(points, adlers, windows) as CUDA tensors -- (n, 4) int64, (n,) int32 holding the uint32
+        bits, (n, 32768) uint8 -- copied on first use and cached per device"""
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if dev not in self._dev:
+            n = self.npoints
+            self._dev[dev] = (torch.from_numpy(self.points.view("<i8").reshape(n, 4).copy()).to(dev),
+                              torch.from_numpy(self.adlers.view("<i4").copy()).to(dev),
+                              torch.from_numpy(self.windows).to(dev))
+        return self._dev[dev]
+
+    def save(self, path) -> None:
+        """numpy.savez of the arrays and the record (load: ZIndex.load)"""
+        import numpy as np
+        meta = np.array([self.format, self.out_len, self.in_used, self.check, self.span], dtype=np.uint64)
+        with open(path, "wb") as f:
+            np.savez(f, points=self.points, adlers=self.adlers, windows=self.windows, meta=meta)
+
+    @classmethod
+    def load(cls, path) -> "ZIndex":
+        import numpy as np
+        with np.load(path, allow_pickle=False) as f:
+            meta = [int(v) for v in f["meta"]]
+            return cls(f["points"], f["adlers"], f["windows"], *meta)
+
+
+def zindex_build(z, fmt: str = "auto", span: int | None = None) -> ZIndex:
+    """Index one zlib stream, gzip member or raw DEFLATE stream that carries no index of its own, on
+    the host (dmx_zindex_build_host; no GPU): one serial decode, a seek point at the first block
+    boundary every `span` bytes of output (default 256 KiB; 1: behind every block that produced
+    output), each with its bit offset, its output range, the Adler-32 of its bytes and the 32 KiB of
+    output in front of it.  The trailer is checked here.  A stream deflate_decompress refuses raises
+    DeflateError with the same status.  Points fall on block boundaries only: a stream that is one
+    block is one point.  Pay once, then inflate_indexed / zindex_read_ranges / zindex_pread."""
+    import numpy as np
+    if fmt not in _BATCH_FMT:
+        raise ValueError("fmt is one of " + ", ".join(_BATCH_FMT))
+    sp = int(span or 0)
+    if sp < 0 or sp > DMX_ZINDEX_MAX_SPAN:
+        raise ValueError("span is 1 .. 2^30 (None or 0: the default)")
+    zp, zn, zk = _buf(z)
+    rec = ZIndexStatus()
+    pts, adl, win = ctypes.c_void_p(0), ctypes.c_void_p(0), ctypes.c_void_p(0)
+    r = lib().dmx_zindex_build_host(zp, zn, _BATCH_FMT[fmt], sp, ctypes.byref(pts), ctypes.byref(adl), ctypes.byref(win),
+                                    ctypes.byref(rec))
+    del zk
+    _check(r, "dmx_zindex_build_host")
+    if rec.status:
+        raise DeflateError(rec.status, "dmx_zindex_build_host")
+    try:
+        n = rec.npoints
+        points = np.frombuffer(ctypes.string_at(pts, 32 * n), dtype=PCHUNK_DTYPE).copy()
+        adlers = np.frombuffer(ctypes.string_at(adl, 4 * n), dtype=np.uint32).copy()
+        windows = np.ctypeslib.as_array(ctypes.cast(win, ctypes.POINTER(ctypes.c_uint8)),
+                                        shape=(n, DMX_ZINDEX_WINDOW)).copy()
+    finally:
+        for p in (pts, adl, win):
+            _libc.free(p)
+    return ZIndex(points, adlers, windows, rec.format, rec.out_len, rec.in_used, rec.check, rec.span)
+
+
+def inflate_points_async(zt, points, adlers, windows, npoints: int, sel, dst_off, nsel: int, out, out_bytes: int, results,
+                         work, status, stream=None) -> int:
+    """dmx_inflate_points_async on caller-owned CUDA tensors, enqueued on `stream` (the current one by
+    default) with no synchronisation, so it can be captured into a graph: zt the compressed bytes;
+    points / adlers / windows as ZIndex.cuda() returns them (adlers None: no verification); sel an
+    int32 tensor of nsel point numbers or None (entry e is point e); dst_off an int64 tensor of nsel
+    offsets into out or None (the points' own out_off); results 32 x nsel bytes (BResult records);
+    work a uint8 tensor of lib().dmx_inflate_points_work(nsel) bytes (256-byte aligned); status a
+    16-byte tensor (BatchStatus).  Returns the call's own return code; the outcomes are in the records."""
+    import torch
+    dev = work.device
+    with torch.cuda.device(dev):
+        s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        return lib().dmx_inflate_points_async(_ptr(zt), zt.numel() if zt is not None else 0, _ptr(points), _ptr(adlers),
+                                              _ptr(windows), npoints, _ptr(sel), _ptr(dst_off), nsel, _ptr(out), out_bytes,
+                                              ctypes.c_void_p(results.data_ptr()), ctypes.c_void_p(work.data_ptr()),
+                                              work.numel(), ctypes.c_void_p(status.data_ptr()), ctypes.c_void_p(s))
+
+
+def _points_decode(zt, index: ZIndex, sel, dst, total: int, verify: bool, what: str):
+    """decode the points `sel` (numpy, None: all) of index to `dst` (numpy offsets, None: their own
+    out_off) of a fresh tensor of `total` bytes; raises for the first entry with a status"""
+    import numpy as np
+    import torch
+    if zt.numel() and (zt.dtype != torch.uint8 or not zt.is_cuda or not zt.is_contiguous()):
+        raise ValueError(what + " takes a contiguous uint8 CUDA tensor")
+    dev = zt.device
+    pt, at, wt = index.cuda(dev)
+    n = index.npoints if sel is None else int(sel.shape[0])
+    out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+    if n == 0:
+        return out[:total]
+    st = torch.empty(2, dtype=torch.int64, device=dev)
+    res = torch.empty(4 * n, dtype=torch.int64, device=dev)
+    work = torch.empty(int(lib().dmx_inflate_points_work(n)), dtype=torch.uint8, device=dev)
+    sel_t = None if sel is None else torch.from_numpy(np.ascontiguousarray(sel, dtype=np.uint32).view(np.int32).copy()).to(dev)
+    dst_t = None if dst is None else torch.from_numpy(np.ascontiguousarray(dst, dtype=np.int64)).to(dev)
+    _check(inflate_points_async(zt, pt, at if verify else None, wt, index.npoints, sel_t, dst_t, n, out, total, res, work, st),
+           "dmx_inflate_points_async")
+    rec = BatchStatus.from_buffer_copy(st.cpu().numpy().tobytes())
+    if rec.nfailed:
+        bad = res.view(n, 4)[rec.first_bad].cpu().numpy().view(np.uint8).view(BRESULT_DTYPE)
+        k = rec.first_bad if sel is None else int(sel[rec.first_bad])
+        raise DeflateError(int(bad["status"][0]), f"{what}: point {k}")
+    return out[:total]
+
+
+def inflate_indexed(zt, index: ZIndex, verify: bool = True):
+    """The whole output of an indexed stream that lies in device memory (dmx_inflate_points_async):
+    zt a contiguous uint8 CUDA tensor with the stream zindex_build indexed, every point a wave of its
+    own, all in parallel.  verify: every point's Adler-32 is compared on the device.  Returns a uint8
+    CUDA tensor of index.out_len bytes; raises DeflateError with the status of the first bad point."""
+    return _points_decode(zt, index, None, None, index.out_len, verify, "inflate_indexed")
+
+
+_GATHER_CHUNK = 1 << 22
+
+
+def zindex_read_ranges(zt, index: ZIndex, ranges, verify: bool = True):
+    """Many ranges of the decoded bytes of an indexed stream in device memory: ranges is an (n, 2)
+    array of (off, len), in any order, overlapping or repeated; only the points they touch are
+    decoded, once each, back to back into a scratch tensor, and the bytes asked for are gathered from
+    it.  Returns (out, offsets) as bgzf_read_ranges: the bytes packed back to back as a uint8 CUDA
+    tensor and an int64 CUDA tensor of n + 1 with range q at out[offsets[q]:offsets[q + 1]].  An empty
+    range and one that ends at out_len are legal; one that reaches beyond out_len is a ValueError.
+    Device memory: the scratch tensor (the touched points, whole), the output, and at most 128 MiB of
+    index tensors for the gather, which runs over groups of ranges of 4 MiB."""
+    import numpy as np
+    import torch
+    a = np.asarray(ranges, dtype=np.int64).reshape(-1, 2)
+    off, ln = a[:, 0], a[:, 1]
+    if a.size and (off.min() < 0 or ln.min() < 0 or int((off + ln).max()) > index.out_len):
+        raise ValueError(f"a range lies outside the {index.out_len} decoded bytes")
+    dev = zt.device
+    offsets_h = np.concatenate(([0], np.cumsum(ln))).astype(np.int64)
+    total = int(offsets_h[-1])
+    offsets = torch.from_numpy(offsets_h).to(dev)
+    if total == 0:
+        return torch.empty(0, dtype=torch.uint8, device=dev), offsets
+    po = index.points["out_off"].astype(np.int64)
+    live = ln > 0
+    first = np.searchsorted(po, off[live], side="right") - 1            # the point that holds the first byte
+    lastp = np.searchsorted(po, off[live] + ln[live] - 1, side="right") - 1   # ... and the last
+    touched = np.zeros(index.npoints + 1, dtype=np.int64)
+    np.add.at(touched, first, 1)
+    np.add.at(touched, lastp + 1, -1)
+    sel = np.nonzero(np.cumsum(touched[:-1]) > 0)[0]
+    plen = index.points["out_len"][sel].astype(np.int64)
+    dst = np.concatenate(([0], np.cumsum(plen)))
+    scratch = _points_decode(zt, index, sel, dst[:-1], int(dst[-1]), verify, "zindex_read_ranges")
+    # where the points' bytes lie in the scratch: output offset o of point sel[j] is at dst[j] + o - out_off
+    shift = np.zeros(index.npoints, dtype=np.int64)
+    shift[sel] = dst[:-1] - po[sel]
+    src0 = np.zeros(a.shape[0], dtype=np.int64)
+    src0[live] = off[live] + shift[first]   # (touched points are consecutive in the scratch along a range)
+    # the gather, in groups of ranges of at most _GATHER_CHUNK bytes: the index tensors of a group are
+    # about 32 bytes per byte gathered, so they stay below 128 MiB whatever is asked for; a range longer
+    # than that is one slice copy
+    out = torch.empty(total, dtype=torch.uint8, device=dev)
+    q, nr = 0, a.shape[0]
+    while q < nr:
+        if ln[q] >= _GATHER_CHUNK:
+            out[offsets_h[q]:offsets_h[q + 1]] = scratch[src0[q]:src0[q] + ln[q]]
+            q += 1
+            continue
+        e = int(np.searchsorted(offsets_h, offsets_h[q] + _GATHER_CHUNK, side="right")) - 1   # offsets_h[e] - offsets_h[q] <= the chunk
+        ln_t = torch.from_numpy(ln[q:e].copy()).to(dev)
+        nb = int(offsets_h[e] - offsets_h[q])
+        if nb:
+            rel = torch.from_numpy(src0[q:e] - (offsets_h[q:e] - offsets_h[q])).to(dev)   # source minus place in the group
+            idx = torch.repeat_interleave(rel, ln_t) + torch.arange(nb, dtype=torch.int64, device=dev)
+            out[offsets_h[q]:offsets_h[e]] = scratch[idx]
+        q = e
+    return out, offsets
+
+
+def zindex_pread(zt, index: ZIndex, off: int, n: int, verify: bool = True):
+    """Bytes [off, off + n) of the decoded bytes of an indexed stream in device memory: a uint8 CUDA
+    tensor.  Only the points the range touches are decoded.  A range beyond out_len is a ValueError."""
+    return zindex_read_ranges(zt, index, [[off, n]], verify)[0]
 
 
 _EBATCH_FMT = {"zlib": DMX_ZLIB, "gzip": DMX_GZIP, "raw": DMX_F_FINAL}

@@ -471,6 +471,176 @@ int dmx_inflate_dict_host(const void* z, uint64_t n, uint32_t fmt, const void* d
     return 0;
 }
 
+/* The seek-point index of one foreign stream (include/dmx.h: dmx_zindex_build_host; DESIGN.md §3.1
+ * "Seek points"): one serial, exact decode with the block routines above, a point at the first block
+ * boundary at which the output since the point before is >= span.  The output is not kept: at a block
+ * boundary, once it has passed ZX_KEEP bytes, the buffer is cut back to its last 32 KiB (all a
+ * distance reaches, and all a point's window needs), so the builder holds the largest block plus
+ * ZX_KEEP + 32 KiB at most; the checks (Adler-32 per point, Adler-32 or CRC-32 + ISIZE of the stream)
+ * are folded block by block in front of the cut. */
+#define ZX_KEEP (1u << 20)
+
+static uint32_t adler32_more(uint32_t adl, const uint8_t* d, size_t n) {
+    uint32_t a = adl & 0xFFFFu, b = adl >> 16;
+    while (n) {
+        size_t k = n < 5552 ? n : 5552;
+        n -= k;
+        while (k--) { a += *d++; b += a; }
+        a %= 65521u;
+        b %= 65521u;
+    }
+    return (b << 16) | a;
+}
+
+typedef struct {
+    dmx_zpoint* pts;
+    uint32_t* adl;
+    uint8_t* win;
+    uint64_t n, cap;
+} zx_arrays;
+
+/* point n = {bit, 0, out_off, 0} with the window in front of out_off: the last wlen bytes of
+ * buf[0, blen), right-aligned in the slot */
+static int zx_push(zx_arrays* a, uint64_t bit, uint64_t out_off, const uint8_t* buf, size_t blen) {
+    if (a->n == 0xFFFFFFFFull) return -(int)E_RANGE;
+    if (a->n == a->cap) {
+        const uint64_t nc = a->cap ? a->cap * 2 : 16;
+        dmx_zpoint* p = (dmx_zpoint*)realloc(a->pts, nc * sizeof(dmx_zpoint));
+        if (p) a->pts = p;
+        uint32_t* q = (uint32_t*)realloc(a->adl, nc * sizeof(uint32_t));
+        if (q) a->adl = q;
+        uint8_t* w = (uint8_t*)realloc(a->win, nc * (uint64_t)DMX_ZINDEX_WINDOW);
+        if (w) a->win = w;
+        if (!p || !q || !w) return -(int)E_MALLOC;
+        a->cap = nc;
+    }
+    const size_t wlen = out_off < DMX_ZINDEX_WINDOW ? (size_t)out_off : DMX_ZINDEX_WINDOW;
+    uint8_t* slot = a->win + a->n * (uint64_t)DMX_ZINDEX_WINDOW;
+    memset(slot, 0, DMX_ZINDEX_WINDOW - wlen);
+    if (wlen) memcpy(slot + (DMX_ZINDEX_WINDOW - wlen), buf + (blen - wlen), wlen);
+    a->pts[a->n].bit = bit;
+    a->pts[a->n].end_bit = 0;
+    a->pts[a->n].out_off = out_off;
+    a->pts[a->n].out_len = 0;
+    a->adl[a->n] = 1;
+    a->n++;
+    return 0;
+}
+
+int dmx_zindex_build_host(const void* z, uint64_t zbytes, uint32_t fmt, uint32_t span, dmx_zpoint** points,
+                          uint32_t** adlers, uint8_t** windows, dmx_zindex_status* st) {
+    if (!st || !points || !adlers || !windows || (!z && zbytes) || fmt > DMX_BATCH_RAW) return -(int)E_INVAL;
+    if (span > DMX_ZINDEX_MAX_SPAN) return -(int)E_RANGE;
+    *points = NULL;
+    *adlers = NULL;
+    *windows = NULL;
+    memset(st, 0, sizeof(*st));
+    st->span = span ? span : DMX_ZINDEX_DEF_SPAN;
+    st->format = fmt == DMX_BATCH_AUTO ? DMX_BATCH_ZLIB : fmt;
+    ist s;
+    memset(&s, 0, sizeof(s));
+    s.in = (const uint8_t*)z;
+    s.n = (size_t)zbytes;
+    /* the framing, as dmx_frame_head (dmx_gz_head.h) and deflate_decompress read it */
+    if (fmt != DMX_BATCH_RAW) {
+        if (s.n < 2) { st->status = -(int)E_ZHEAD; return 0; }
+        const int cmf = s.in[0], flg = s.in[1];
+        const int magic = cmf == 0x1F && flg == 0x8B;
+        if (fmt == DMX_BATCH_AUTO && magic) st->format = DMX_BATCH_GZIP;
+        if (st->format == DMX_BATCH_GZIP) {
+            size_t body = 0;
+            const long e = magic ? gzip_header(s.in, s.n, &body) : -(long)E_ZHEAD;
+            if (e) { st->status = (int)e; return 0; }
+            s.pos = body;
+        } else {
+            int e = 0;
+            if ((cmf & 0x0F) != 8) e = -(int)E_ZCMPMT;
+            else if ((cmf >> 4) > 7) e = -(int)E_ZSLWIN;
+            else if (((cmf << 8) | flg) % 31) e = -(int)E_ZFCHCK;
+            else if (flg & 0x20) e = -(int)E_ZPDICT;
+            if (e) { st->status = e; return 0; }
+            s.pos = 2;
+        }
+    }
+    const int gz = st->format == DMX_BATCH_GZIP;
+    zx_arrays a;
+    memset(&a, 0, sizeof(a));
+    uint64_t total = 0;        /* output bytes in front of s.out[0] plus s.olen: see done */
+    uint64_t cut = 0;          /* output bytes no longer in the buffer */
+    size_t done = 0;           /* s.out[0, done) is folded into the checks */
+    uint32_t whole = gz ? 0u : 1u;   /* the stream's CRC-32 / Adler-32 so far */
+    int r = zx_push(&a, 8ull * s.pos, 0, NULL, 0), last = 0;
+    while (!r && !last) {
+        last = bits(&s, 1);
+        const int type = bits(&s, 2);
+        if (s.err) { r = s.err; break; }
+        if (type == 0) r = stored(&s);
+        else if (type == 1) r = fixed(&s);
+        else if (type == 2) r = dynamic(&s);
+        else r = -(int)E_ZBTYPE;
+        if (r) break;
+        /* the block's bytes: into the point's Adler-32 and the stream's check */
+        dmx_zpoint* p = &a.pts[a.n - 1];
+        const size_t nb = s.olen - done;
+        if (nb) {
+            a.adl[a.n - 1] = adler32_more(a.adl[a.n - 1], s.out + done, nb);
+            whole = gz ? dmx_crc32_host(whole, s.out + done, nb) : adler32_more(whole, s.out + done, nb);
+            p->out_len += nb;
+            done = s.olen;
+        }
+        total = cut + s.olen;
+        const uint64_t bit = 8ull * s.pos - (uint64_t)s.bitcnt;
+        if (!last && p->out_len >= st->span) {   /* the next block's BFINAL bit starts a point */
+            p->end_bit = bit;
+            r = zx_push(&a, bit, total, s.out, s.olen);
+        } else if (last) {
+            p->end_bit = bit;
+        }
+        if (s.olen >= ZX_KEEP + DMX_ZINDEX_WINDOW) {   /* keep what a distance can still reach */
+            memmove(s.out, s.out + (s.olen - DMX_ZINDEX_WINDOW), DMX_ZINDEX_WINDOW);
+            cut += s.olen - DMX_ZINDEX_WINDOW;
+            s.olen = done = DMX_ZINDEX_WINDOW;
+        }
+    }
+    if (!r) {   /* the trailer, as inflate_trailer checks it */
+        s.bitbuf >>= s.bitcnt & 7;
+        s.bitcnt -= s.bitcnt & 7;
+        uint32_t want = 0, isize = 0;
+        if (gz) {
+            for (int k = 0; k < 4; k++) want |= (uint32_t)bits(&s, 8) << (8 * k);
+            for (int k = 0; k < 4; k++) isize |= (uint32_t)bits(&s, 8) << (8 * k);
+            if (s.err || want != whole) r = -(int)E_CRC;
+            else if (isize != (uint32_t)total) r = -(int)E_LEN;
+        } else if (st->format == DMX_BATCH_ZLIB) {
+            for (int k = 0; k < 4; k++) want = (want << 8) | (uint32_t)bits(&s, 8);
+            if (s.err || want != whole) r = -(int)E_ZADL32;
+        }
+        st->check = want;
+    }
+    free(s.out);
+    if (r) {
+        free(a.pts);
+        free(a.adl);
+        free(a.win);
+        if (r == -(int)E_MALLOC || r == -(int)E_RANGE) return r;   /* the builder's own, not the stream's */
+        st->status = r;
+        st->check = 0;
+        return 0;
+    }
+    st->out_len = total;
+    st->in_used = (uint64_t)s.pos - (uint64_t)(s.bitcnt / 8);
+    st->npoints = (uint32_t)a.n;
+    /* the arrays grew by doubling: give back what is not used (a realloc that fails leaves them as they are) */
+    void* t;
+    if ((t = realloc(a.pts, a.n * sizeof(dmx_zpoint)))) a.pts = (dmx_zpoint*)t;
+    if ((t = realloc(a.adl, a.n * sizeof(uint32_t)))) a.adl = (uint32_t*)t;
+    if ((t = realloc(a.win, a.n * (uint64_t)DMX_ZINDEX_WINDOW))) a.win = (uint8_t*)t;
+    *points = a.pts;
+    *adlers = a.adl;
+    *windows = a.win;
+    return 0;
+}
+
 /* The block index of a BGZF file (SAM/BAM specification §4.1; include/dmx.h): a series of gzip
  * members with FEXTRA set, each carrying its own size - 1 as BSIZE in the "BC" subfield
  * (SI1 'B', SI2 'C', SLEN 2), so the walk reads headers and trailers only.  The DEFLATE data

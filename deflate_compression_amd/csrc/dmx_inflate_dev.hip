@@ -1216,6 +1216,120 @@ __global__ __launch_bounds__(64) void dmx_inflate_batch_kernel(const uint8_t* __
 }
 
 // ------------------------------------------------------------------------------------
+// Seek points (dmx_inflate_points_async, include/dmx.h; DESIGN.md 3.1 "Seek points"): entries of
+// the index dmx_zindex_build_host made of one foreign stream, a wave each, with the batch decode's
+// geometry -- one wave per workgroup, the IW ring, workgroups claiming entries from the counter in
+// d_work, the first-level tables behind it.  Entry e is point k = sel[e]: its window is output that
+// was flushed before the point began, exactly a preset dictionary (the arithmetic above IBatchDict):
+// the wlen = min(out_off, IW) bytes at the end of slot k prime win[0, wlen), op = fl = wlen,
+// base = dst - wlen, cap = out_len + wlen.  A point with out_off forged to 0 starts at op = 0, so
+// what the ring held for the entry before it is never read (dist > op is -E_HUFDIS).
+// The reader is set up on the point's own bytes, z[bit >> 3, ceil(end_bit / 8)), and sought to
+// bit & 7: zeros past them, an overrun is -E_LEN through ib_status, and only the extent of one point
+// has to fit the reader's 32-bit positions.  Blocks are decoded until the bits consumed are exactly
+// end_bit; a boundary beyond it, or BFINAL short of it, is -E_SZ, and so is an output that is not
+// out_len at the end.  The capacity is always the finite out_len + wlen: the symbol loop ends by
+// capacity, a block without output consumes input and the loop over blocks ends at end_bit, so every
+// loop here is bounded.  The one known cause of a run without end (the measure pass
+// with out_cap = UINT64_MAX behind a stream cut inside a block) needs an unbounded capacity and
+// cannot arise.  Long zero-run streams are not verified on the device (include/dmx.h).
+// ------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void dmx_inflate_points_kernel(const uint8_t* __restrict__ z, uint64_t zbytes,
+                                                                const dmx_zpoint* __restrict__ points,
+                                                                const uint32_t* __restrict__ adler,
+                                                                const uint8_t* __restrict__ windows, uint32_t npoints,
+                                                                const uint32_t* __restrict__ sel,
+                                                                const uint64_t* __restrict__ dst_off, uint32_t nsel,
+                                                                uint8_t* out, uint64_t out_bytes,
+                                                                dmx_bresult* __restrict__ res, uint32_t* __restrict__ gtab,
+                                                                IBatchCtl* __restrict__ ctl,
+                                                                dmx_batch_status* __restrict__ st) {
+    __shared__ InfLDS<IW> S;   // the kernel's one __shared__ object: isym_run addresses the ring from LDS 0
+    uint32_t* gt = gtab + (uint64_t)blockIdx.x * ITAB_WORDS;
+    const uint32_t lane = threadIdx.x;
+    for (;;) {
+        unsigned long long claim = 0;
+        if (lane == 0) claim = atomicAdd(&ctl->next, 1ull);
+        const uint64_t e64 = rfl64(claim);
+        if (e64 >= nsel) break;
+        const uint32_t e = (uint32_t)e64;
+        const uint32_t k = rfl(sel ? sel[e] : e);
+        int err = 0;
+        uint64_t bit = 0, end_bit = 0, out_off = 0, out_len = 0, dst = 0, first = 0, ext = 0;
+        if (k >= npoints) {
+            err = -(int)E_RANGE;
+        } else {
+            bit = rfl64(points[k].bit);
+            end_bit = rfl64(points[k].end_bit);
+            out_off = rfl64(points[k].out_off);
+            out_len = rfl64(points[k].out_len);
+            dst = dst_off ? rfl64(dst_off[e]) : out_off;
+            first = bit >> 3;
+            const uint64_t endb = (end_bit >> 3) + ((end_bit & 7) ? 1u : 0u);   // ceil(end_bit / 8)
+            if (bit >= end_bit || endb > zbytes) err = -(int)E_RANGE;
+            else if ((ext = endb - first) > 0xFFFFFFF0ull) err = -(int)E_RANGE;
+            if (dst > out_bytes || out_len > out_bytes - dst) err = -(int)E_RANGE;
+        }
+        const uint32_t wlen = out_off < IW ? (uint32_t)out_off : (uint32_t)IW;
+        uint64_t olen = 0;
+        uint32_t check = 0;
+        IBits r;
+        IOut o;
+#ifdef DMX_INF_STAMPS
+        for (int q = 0; q < INF_NST; q++) o.st[q] = 0;
+#endif
+        o.out = out;
+        o.base = dst - wlen;   // (wraps where dst < wlen: meant, as in the batch kernel -- only ever used with p >= fl >= wlen added)
+        o.ob = 0;
+        o.cap = out_len + wlen;
+        o.op = wlen;
+        o.fl = wlen;
+        o.a = 1;
+        o.b = 0;
+        if (!err) {
+            if (wlen) iprime(S.win, windows + (uint64_t)k * IW + (IW - wlen), wlen, lane);
+            ib_init(r, z + first, ext);
+            ib_seek(r, bit & 7);
+            const uint64_t endrel = end_bit - 8 * first;   // in the reader's bits (relative to z + first)
+            // the loop's exits are made uniform for the compiler too (readfirstlane), as in the batch kernel
+            for (;;) {
+                bool last = false;
+                const int e2 = ib_status(r, iblock<true, true, IW, false, true>(S, r, o, gt, lane, last));
+                err = (int)rfl((uint32_t)e2);
+                if (err) break;
+                const uint64_t used = (uint64_t)rfl(r.wi) * 32 - rfl(r.bc) - 8ull * r.lo;
+                if (used == endrel) break;
+                if (used > endrel || rfl(last ? 1u : 0u)) { err = -(int)E_SZ; break; }
+            }
+        }
+        if (!err) {
+            io_flush<true, true>(S, o, o.op, lane);
+            olen = o.ob + o.op - wlen;
+            check = (o.b << 16) | o.a;
+            if (olen != out_len) err = -(int)E_SZ;
+            else if (adler && rfl(adler[k]) != check) err = -(int)E_ZADL32;
+        }
+        if (lane == 0) {
+            dmx_bresult v;
+            v.status = err;
+            v.format = DMX_BATCH_RAW;
+            v.out_len = err ? 0 : olen;
+            v.in_used = err ? 0 : ext;
+            v.check = err ? 0 : check;
+            v.reserved = 0;
+            res[e] = v;
+            if (err) {
+                atomicAdd(&st->nfailed, 1u);
+                atomicMin(&st->first_bad, e);
+            } else {
+                atomicAdd((unsigned long long*)&st->total_out, (unsigned long long)olen);
+            }
+        }
+        __syncthreads();   // the ring and the small arrays are the next entry's
+    }
+}
+
+// ------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------
 
@@ -1426,6 +1540,36 @@ extern "C" int dmx_inflate_batch_dict_async(const void* d_z, uint64_t zbytes, co
     if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
     if (measure || fmt == DMX_BATCH_ZLIB || fmt == DMX_BATCH_RAW) return 0;   // no gzip member to finish
     return dmx_crc32_batch_launch(d_out, out_bytes, d_streams, nstreams, d_results, d_status, s);
+}
+
+// Seek points: d_work as the batch decode's -- [IBatchCtl, 256 B][first-level tables].  The grid is
+// the batch kernel's too: the same InfLDS<IW> is the limit per CU.
+extern "C" uint64_t dmx_inflate_points_work(uint32_t nsel) { return dmx_inflate_batch_work(nsel); }
+
+extern "C" int dmx_inflate_points_async(const void* d_z, uint64_t zbytes, const dmx_zpoint* d_points, const uint32_t* d_adler,
+                                        const void* d_windows, uint32_t npoints, const uint32_t* d_sel,
+                                        const uint64_t* d_dst_off, uint32_t nsel, void* d_out, uint64_t out_bytes,
+                                        dmx_bresult* d_results, void* d_work, uint64_t work_bytes, dmx_batch_status* d_status,
+                                        void* stream) {
+    if (!d_results || !d_status || !d_work || ((!d_points || !d_windows || !d_out) && nsel) || (!d_z && zbytes))
+        return -(int)E_INVAL;
+    if (((uintptr_t)d_points & 7) || ((uintptr_t)d_dst_off & 7) || ((uintptr_t)d_results & 7) || ((uintptr_t)d_status & 7) ||
+        ((uintptr_t)d_adler & 3) || ((uintptr_t)d_sel & 3))
+        return -(int)E_INVAL;
+    if (((uintptr_t)d_work & 255) || work_bytes < dmx_inflate_points_work(nsel)) return -(int)E_INVAL;
+    hipStream_t s = (hipStream_t)stream;
+    IBatchCtl* ctl = (IBatchCtl*)d_work;
+    uint32_t* gtab = (uint32_t*)((uint8_t*)d_work + 256);
+    hipLaunchKernelGGL(dmx_inflate_batch_clear_kernel, dim3(1), dim3(1), 0, s, ctl, d_status);
+    if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
+    if (!nsel) return 0;
+    const uint32_t resident = ibatch_resident();
+    if (!resident) return -(int)E_DEVICE;
+    const uint32_t grid = nsel < resident ? nsel : resident;
+    hipLaunchKernelGGL(dmx_inflate_points_kernel, dim3(grid), dim3(64), 0, s, (const uint8_t*)d_z, zbytes, d_points, d_adler,
+                       (const uint8_t*)d_windows, npoints, d_sel, d_dst_off, nsel, (uint8_t*)d_out, out_bytes, d_results, gtab,
+                       ctl, d_status);
+    return hipGetLastError() == hipSuccess ? 0 : -(int)E_DEVICE;
 }
 
 // ------------------------------------------------------------------------------------

@@ -714,6 +714,83 @@ typedef struct { int32_t status; uint32_t format; uint64_t out_len; uint64_t in_
                  uint64_t work_len; } dmx_par_status;                             /* 56 bytes */
 int dmx_inflate_parallel_plan_host(const void* z, uint64_t zbytes, uint32_t fmt, uint32_t chunk_bytes,
                                    dmx_pchunk* chunks, uint32_t cap, dmx_par_status* st);
+/* One foreign stream, indexed once and read many times: seek points (csrc/dmx_inflate.c,
+ * csrc/dmx_inflate_dev.hip; DESIGN.md §3.1 "Seek points").  The index of zran, indexed_gzip and
+ * rapidgzip's --export-index: the stream is decoded once, serially and exactly, on the host, and at
+ * block boundaries about every `span` bytes of output a point records the bit offset, the output
+ * offset and the 32 KiB of output in front of it.  From then on every point decodes on its own: a
+ * whole decode is one wave per point, a range read decodes only the points it touches.  No search,
+ * no speculation: nothing of the plan above is used.
+ * dmx_zindex_build_host: host only, no GPU.  z[0, zbytes) under fmt (DMX_BATCH_AUTO / ZLIB / GZIP /
+ * RAW, dmx_frame_head's rules) is decoded with deflate_decompress's block routines and its trailer
+ * (Adler-32, or CRC-32 and ISIZE) is checked here, once; a stream deflate_decompress refuses gets
+ * the same status in st->status and no index (the three arrays stay NULL).  Bytes behind the trailer
+ * are ignored; in_used says where they start (the next member of a multi-member .gz: the caller's).
+ *   point 0 is the first block of the body: out_off 0, no window.  A further point is placed at the
+ *   first block boundary at which the output since the point before is >= span; the boundary is the
+ *   bit of the next block's BFINAL bit, before any stored block's alignment.  span: 0 is
+ *   DMX_ZINDEX_DEF_SPAN (256 KiB: 12.5 % of the output in windows, about 400 points per 100 MB), else
+ *   1 .. DMX_ZINDEX_MAX_SPAN (2^30); 1 makes every block that produced output end a point.  Points fall on
+ *   block boundaries only, so a stream that is one giant block is one point, and a point is as long as
+ *   the blocks that make up its span (zlib's blocks of text hold some 60 KB; of zeros 4.2 MB).  An
+ *   empty final block behind a boundary is a last point with out_len 0.
+ *   points[k] (dmx_zpoint = dmx_pchunk): bit, end_bit (the bit of the next point; the last point's is
+ *   the bit behind the final block's last bit), out_off (the exclusive scan of out_len), out_len.
+ *   adlers[k]: the Adler-32 of that point's out_len bytes.  windows + k * DMX_ZINDEX_WINDOW: a slot of
+ *   32 768 bytes with the wlen = min(out_off, 32768) bytes in front of out_off right-aligned in it,
+ *   zeros before them.
+ * The three arrays are malloc'd (the caller frees each with free(), as dmx_inflate_dict_host's
+ * output).  The record (40 bytes): status, format (1, 2, 3), out_len, in_used through the trailer,
+ * check (the stored Adler-32 / CRC-32; 0 for raw), npoints, span (the value used).  After a stream
+ * error everything but status, format and span is 0.  Memory: the output is not kept -- the builder
+ * holds the largest block plus 1 MiB + 32 KiB of it, and the index; the index's arrays grow by doubling
+ * while it is built, so at their peak they take up to twice their final size (32 804 bytes a point),
+ * and are cut back to it before they are returned.  Returns 0 with the record in
+ * *st, -E_INVAL (st or an array pointer NULL, z NULL with zbytes > 0, fmt above 3), -E_RANGE (span
+ * above 2^30, more than 2^32 - 1 points) or -E_MALLOC.
+ * dmx_inflate_points_async: nsel entries of such an index decoded on the device, side by side, one
+ * wave each, with dmx_inflate_batch_async's geometry and promises: a dmx_bresult per entry, a failing
+ * entry never changes a neighbour's bytes or result, no byte outside an entry's own
+ * [dst, dst + out_len) is written, two launches (reset, decode), no allocation, no host
+ * synchronisation, a linear chain that can be captured into a graph.  Entry e decodes point
+ * k = d_sel[e] (d_sel NULL: k = e) to d_out + d_dst_off[e] (d_dst_off NULL: the point's own out_off):
+ * the ring is primed with the point's window, the reader is set up on the point's own bytes
+ * z[bit >> 3, ceil(end_bit / 8)) only -- zeros past them, so an overrun is -E_LEN, and streams above
+ * 4 GiB work: only one point's compressed extent is bounded by 0xFFFFFFF0 -- and blocks are decoded
+ * until exactly end_bit bits are consumed.  Statuses: the stream table's for what the blocks hold;
+ * -E_SZ for a block boundary beyond end_bit, BFINAL short of end_bit, more than out_len bytes, or
+ * fewer at the end; -E_HUFDIS for a distance before the window; -E_ZADL32 where d_adler is given and
+ * d_adler[k] is not the Adler-32 of the bytes produced (per point, so any subset verifies; there is
+ * no whole-stream check on the device); -E_RANGE, with nothing of the entry read or written, for
+ * k >= npoints, bit >= end_bit, end_bit > 8 * zbytes, an extent above 0xFFFFFFF0, or
+ * [dst, dst + out_len) outside d_out[0, out_bytes).  Destinations that overlap are the caller's error.
+ * d_results[e]: status, format 3, out_len, in_used = the bytes of the point's extent, check = the
+ * computed Adler-32; after an error the last three are 0.  d_status: dmx_batch_status over the
+ * entries.  The capacity of an entry is always the finite out_len, so every loop ends by capacity or
+ * by input.  Long zero-run streams (zlib's multi-megabyte blocks whose literal/length code is two
+ * 1-bit codes) are indexed by the host builder but their device decode is unverified: two other
+ * instantiations of the block decoder did not return on them, cause not found.
+ * d_work: 256-byte aligned, work_bytes >= dmx_inflate_points_work(nsel) (= dmx_inflate_batch_work).
+ * Returns before any device call: -E_INVAL (d_results, d_status, d_work NULL; d_points or d_windows
+ * NULL with nsel > 0; d_z NULL with zbytes > 0; d_out NULL with nsel > 0; d_points, d_dst_off,
+ * d_results or d_status not 8-byte, d_adler or d_sel not 4-byte aligned; d_work not 256-byte aligned
+ * or work_bytes too small); else 0 or -E_DEVICE. */
+#define DMX_ZINDEX_WINDOW 32768u
+#define DMX_ZINDEX_DEF_SPAN (256u << 10)
+#define DMX_ZINDEX_MAX_SPAN (1u << 30)
+typedef dmx_pchunk dmx_zpoint;                                                    /* 32 bytes: a seek point */
+typedef struct { int32_t status; uint32_t format; uint64_t out_len; uint64_t in_used;
+                 uint32_t check; uint32_t npoints; uint32_t span; uint32_t reserved; } dmx_zindex_status; /* 40 bytes */
+int dmx_zindex_build_host(const void* z, uint64_t zbytes, uint32_t fmt, uint32_t span, dmx_zpoint** points,
+                          uint32_t** adlers, uint8_t** windows, dmx_zindex_status* st);
+uint64_t dmx_inflate_points_work(uint32_t nsel);
+int dmx_inflate_points_async(const void* d_z, uint64_t zbytes, const dmx_zpoint* d_points,
+                             const uint32_t* d_adler,     /* NULL: no verification */
+                             const void* d_windows, uint32_t npoints,
+                             const uint32_t* d_sel,       /* NULL: entry e is point e */
+                             const uint64_t* d_dst_off,   /* NULL: the points' own out_off */
+                             uint32_t nsel, void* d_out, uint64_t out_bytes, dmx_bresult* d_results,
+                             void* d_work, uint64_t work_bytes, dmx_batch_status* d_status, void* stream);
 /* Batches of independent buffers into independent streams (csrc/dmx_encode_batch.hip):
  * the encode's counterpart of dmx_inflate_batch_async.  nstreams buffers become nstreams complete
  * zlib streams, gzip members or raw DEFLATE streams, every one decodable on its own, in one chain of
