@@ -34,6 +34,7 @@
 
 #include "dmx_internal.h"
 #include "dmx_extbits.h"
+#include "dmx_walk.h"
 #include "../../include/dmx.h"
 
 #define MAXLEN 258
@@ -785,19 +786,23 @@ __device__ __forceinline__ void pair_from(uint32_t a0, uint32_t a1, uint32_t b0,
 template <bool DICT>
 __device__ __forceinline__ uint32_t short_result(MatchLDS& L, uint32_t k, uint32_t i, uint32_t jkey,
                                                  const uint32_t* __restrict__ hbk) {
+    // Under the caller's one mask (act && !push) and with no branch on the kind: the length
+    // stored is a saturating m - 3 (0 for a literal), the literal bit an atomic OR of a selected
+    // value, the nibble a select.  (store_short keeps its branch: the queue's entries are all
+    // matches, and there the same form was slower.)
     const uint32_t m = jkey >> 3;
-    uint32_t len = m >= 3 ? m : 0u, j = m >= 3 ? 8u - (jkey & 7u) : 0u;
+    uint32_t len = m, j = 8u - (jkey & 7u);
+    bool has = m >= 3;
     if (DICT) {
-        const uint32_t hw = hbk[k];
-        if ((hw >> 16) > len) { len = hw >> 16; j = NIB_HIST; }
+        const uint32_t hl = hbk[k] >> 16;
+        const bool hist = hl > (has ? m : 0u);
+        len = hist ? hl : len;
+        j = hist ? NIB_HIST : j;
+        has = has || hist;
     }
-    if (len == 0) {
-        atomicOr(&L.lit[i >> 5], 1u << (i & 31));
-        L.len8[i] = 0;
-        return 0;
-    }
-    L.len8[i] = (uint8_t)(len - 3);
-    return j;
+    L.len8[i] = (uint8_t)__builtin_elementwise_sub_sat(len, 3u);
+    atomicOr(&L.lit[i >> 5], has ? 0u : 1u << (i & 31));
+    return has ? j : 0u;
 }
 template <bool DICT, int KK>
 __device__ __forceinline__ uint32_t search_pairs(MatchLDS& L, uint32_t bn, uint32_t tid, bool stamp, uint64_t& tdef,
@@ -1318,37 +1323,12 @@ __device__ __forceinline__ uint32_t search_positions(MatchLDS& L, uint32_t bn, i
 }
 
 // Resolve segment s (positions [32s, 32s+32)) for a path entering at e >= 32s, against the
-// path word m of that segment: if the walk from e meets one of m's positions the rest
-// coincides (the next-function is deterministic).  Scalar code: every input is uniform.
+// path word m of that segment (exit x): if the walk from e meets one of m's positions the rest
+// coincides (the next-function is deterministic).  The walk is dmx_walk_segment (dmx_walk.h):
+// a literal run and the match behind it per trip, one len8 read per trip.
 __device__ __forceinline__ uint32_t resolve_word(const MatchLDS& L, uint32_t lo, uint32_t e, uint32_t bn, uint32_t m,
                                                  uint32_t lw, uint32_t x, uint32_t& nm_out, bool& merged) {
-    merged = false;
-    if (e >= lo + 32 || e >= bn) { nm_out = 0; return e; }
-    uint32_t nm = 0, p = e;
-    while (p < lo + 32 && p < bn) {
-        // a run of literals in one step (their bits in lw, up to the segment end or bn): every
-        // position of it is a token start; no LDS read
-        const uint32_t sh = p - lo;
-        const uint32_t run = min(ffbl_hw(~(lw >> sh)), min(lo + 32u, bn) - p);   // (lit bits past bn may be set by P1b)
-        if (run) {
-            const uint32_t rm = (run >= 32u ? ~0u : ((1u << run) - 1u)) << sh;
-            if (m & rm) {
-                const uint32_t bb = ffbl_hw(m & rm), below = (1u << bb) - 1u;   // the first shared position
-                nm_out = nm | (rm & below) | (m & ~below);
-                merged = true;
-                return x;
-            }
-            nm |= rm;
-            p += run;
-            continue;
-        }
-        const uint32_t bit = 1u << sh;
-        if (m & bit) { nm_out = nm | (m & ~(bit - 1u)); merged = true; return x; }
-        nm |= bit;
-        p += (uint32_t)L.len8[p] + 3u;
-    }
-    nm_out = nm;
-    return p;
+    return dmx_walk_segment<true>(lo, e, bn, lw, m, x, [&L](uint32_t p) { return (uint32_t)L.len8[p]; }, nm_out, merged);
 }
 
 // Lanes of the wave holding the same value v as this lane (among the valid lanes): every
@@ -3357,6 +3337,7 @@ __device__ __forceinline__ void match_block(const uint32_t b, const uint8_t* __r
     // Position p (a match) becomes a literal when p+1 holds a strictly longer match; the
     // walk below then emits the literal and re-decides at p+1 -- exactly the sequential
     // sequential rule (bounded/lazy modes).  Each thread owns one literal word.
+    uint32_t lwseg = 0;   // the segment's literal word after the lazy rule (W1 takes it from here)
     if (mflags & 1u) {   // DMX_F_LAZY
         const uint32_t lw = L.lit[tid];
         const uint32_t nb0 = (tid + 1 < DMX_BLK / 32) ? (L.lit[tid + 1] & 1u) : 1u;
@@ -3373,37 +3354,36 @@ __device__ __forceinline__ void match_block(const uint32_t b, const uint8_t* __r
             const uint32_t nxt = (lv[(bb + 1) >> 2] >> (8 * ((bb + 1) & 3))) & 0xFFu;
             longer |= (nxt > cur ? 1u : 0u) << bb;
         }
-        __syncthreads();
-        L.lit[tid] = lw | (~lw & ~litn & longer);
-        __syncthreads();
+        __syncthreads();   // every thread has read its neighbour's word
+        lwseg = lw | (~lw & ~litn & longer);
+        L.lit[tid] = lwseg;
+        // no barrier here: W1 walks on lwseg, and every other reader of L.lit (the rounds, W2,
+        // W3, P3) comes after the barrier before the permute's stores
+    } else {
+        lwseg = L.lit[tid];
     }
     if (dbg && tid == 0) st_lz = __builtin_amdgcn_s_memtime() - t1;
 
     // ---- P2: greedy path ----
+    uint32_t myexit;   // the exit of this thread's segment on its current path
+    if (tid < JR) L.wexit[tid] = 0;   // the rounds' votes (wexit is free until W2); published with exitp
     {   // W1: speculative walk of every 32-position segment from its start
-        const uint32_t lo = tid << 5, lw = L.lit[tid];   // the segment's literal bits: one read
-        uint32_t m = 0, p = lo;
-        while (p < lo + 32 && p < bn) {
-            // a run of literals in one step (resolve_word); a match reads its length
-            const uint32_t sh = p - lo;
-            const uint32_t run = min(ffbl_hw(~(lw >> sh)), min(lo + 32u, bn) - p);   // (lit bits past bn may be set by P1b)
-            if (run) {
-                m |= (run >= 32u ? ~0u : ((1u << run) - 1u)) << sh;
-                p += run;
-                continue;
-            }
-            m |= 1u << sh;
-            p += (uint32_t)L.len8[p] + 3u;
-        }
+        const uint32_t lo = tid << 5;
+        uint32_t m;
+        bool mg;
+        const uint8_t* len8 = L.len8;
+        myexit = dmx_walk_segment<false>(lo, lo, bn, lwseg, 0u, 0u, [len8](uint32_t p) { return (uint32_t)len8[p]; }, m, mg);
         L.tsm[tid] = m;
-        L.exitp[tid] = p;
+        L.exitp[tid] = myexit;
     }
     {   // the sorted positions are dead: permute the best distances (bucket order) into
         // position order in the same LDS slots, through registers (32 per thread).  Short
         // chains (K <= KE): distance = S[k] - S[k - j] from the winner nibble j of entry k (the
         // history's from its result); longer chains staged the distances in pg (HBM).
-        __syncthreads();
-        if (dbg && tid == 0) st_w1w = __builtin_amdgcn_s_memtime() - t1;
+        // No barrier after W1: it wrote tsm and exitp, these reads touch sorted, the nibble
+        // words and hbk (pg), so the latency-bound walk of some waves runs beside the reads of
+        // others.  The barrier before the stores below also publishes exitp and lit.
+        if (dbg && tid == 0) st_w1w = __builtin_amdgcn_s_memtime() - t1;   // (wave 0's walk: no barrier)
         const uint32_t nvalid = bn > 2 ? bn - 2 : 0;
         uint4 dv[4], pv[4];
         if (kb > 0 && kb <= KE) {
@@ -3504,18 +3484,28 @@ __device__ __forceinline__ void match_block(const uint32_t b, const uint8_t* __r
                 __syncthreads();
                 if (L.ntok <= WALK_SERIAL) { serial = true; break; }
             }
-            const uint32_t e = tid == 0 ? 0u : L.exitp[tid - 1];
-            __syncthreads();
+            // the exits in two copies, read from one and written to the other (the second lives
+            // in the nibble words, dead since the permute's reads and free until P3's token
+            // list): the round's only barrier is its vote.  The own exit stays in a register.
+            const uint32_t* exr = (r & 1u) ? nib_words(L) : L.exitp;
+            uint32_t* exw = (r & 1u) ? L.exitp : nib_words(L);
+            const uint32_t e = tid == 0 ? 0u : exr[tid - 1];
             const bool ch = (tid << 5) < bn && e != entry;   // segments past the block end stay empty
             if (ch) {
                 uint32_t nm;
                 bool mg;
-                const uint32_t x = resolve_word(L, tid << 5, e, bn, L.tsm[tid], L.lit[tid], L.exitp[tid], nm, mg);
+                myexit = resolve_word(L, tid << 5, e, bn, L.tsm[tid], lwseg, myexit, nm, mg);
                 L.tsm[tid] = nm;
-                L.exitp[tid] = x;
                 entry = e;
             }
-            if (!__syncthreads_or(ch)) { conv = true; break; }
+            exw[tid] = myexit;
+            // the vote: a wave with a changed entry sets the round's word (zeroed before W1):
+            // one barrier, where __syncthreads_or makes three around its LDS reduction.  (After
+            // the last round a fast wave's W2 may already have put its exit, which is not 0, into
+            // that round's word: wave JR - 1 starts at (JR - 1) << 11 and an exit never goes back.)
+            if (__builtin_amdgcn_ballot_w64(ch) != 0 && lane == 0) L.wexit[r] = 1u;
+            __syncthreads();
+            if (L.wexit[r] == 0) { conv = true; break; }
         }
         if (dbg && tid == 0) st_rounds = r;
     }
@@ -3540,7 +3530,7 @@ __device__ __forceinline__ void match_block(const uint32_t b, const uint8_t* __r
         {   // W2: each wave resolves its 64 segments assuming it is entered at 2048*wave.
             // Segment words live one per lane; the serial loop runs on uniform values.
             uint32_t myw = L.tsm[tid];
-            const uint32_t myx = L.exitp[tid], myl = L.lit[tid];
+            const uint32_t myx = myexit, myl = lwseg;   // (the current copy of the exits: the own one)
             uint32_t e = wave << 11;
             for (uint32_t j = 0; j < 64; j++) {
                 const uint32_t m = __builtin_amdgcn_readlane(myw, (int)j), x = __builtin_amdgcn_readlane(myx, (int)j),
