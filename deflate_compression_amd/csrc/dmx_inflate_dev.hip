@@ -507,8 +507,16 @@ __device__ __forceinline__ uint32_t lds_addr(const void* p) {
 //            (the segment after next is not wholly inside the stream)
 //   IX_LIM   op >= lim at a literal or a length (a flush the run does not do itself, or the
 //            capacity), or a length that does not fit the capacity
-//   IX_DIST  length decoded into len; the distance code is long or invalid
+//   IX_DIST  length decoded into len and consumed; the distance code is long or invalid, or
+//            the refill in front of it needs a stream segment the run does not rotate into
+//            (then bc <= 32 and the caller's refill comes first)
 //   IX_MATCH len and dist decoded: a distance before the output
+// Both refills (at a token start, and between a length and its distance) rotate the stream
+// segments when their word is the first of vnxt, so wi - wb <= 64 at every refill and at
+// every exit, which is what ib_word's single rotation needs.  (Until the second one did,
+// tokens of one size dividing 32 -- zlib's runs of 2-bit tokens for constant input, at odd bit
+// offsets -- could place every refill of a stretch between length and distance: nothing
+// rotated, and past wb + 128 v_readlane's lane select wrapped onto words already consumed.)
 // Hazards: a lane select written by SALU is 4+ instructions old at each v_readlane (s_nop 3
 // where it is not); the stream prefetch is waited for before it is read and before return;
 // m0 (written by s_set_gpr_idx_on) is restored.
@@ -707,6 +715,12 @@ __device__ __forceinline__ int iblock(InfLDS<W, typename std::conditional<CELL, 
     const uint32_t lta = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_addr(&S.lt));
     static_assert((W * CS) % 16 == 0 && sizeof(ITable) == 672, "the run's ITable offsets (dmx_isym.inc)");
     for (;;) {
+        // The input's end bounds the loop: the reader hands out zeros behind it, and where they
+        // spell literals or matches only the capacity would end a cut stream -- never, with an
+        // unlimited capacity under MEASURE.  The run returns here at least every half ring, so at
+        // most FL + 258 positions are decoded from those zeros (ib_status: -E_LEN).  A valid
+        // stream never has consumed more than it holds while a block is still open.
+        if (ib_past(r)) { err = -(int)E_LEN; break; }
         uint32_t lim = RING ? min(capr, o.fl + FL) : capr, fl = o.fl;
         uint32_t len, dist;
         const uint32_t ex = isym_run<W, CELL>(r, op, lim, fl, capr, fok, gpos0, dfl, lta, tgl, tgd, lane * 4, lane, gpos0,
@@ -1230,9 +1244,9 @@ __global__ __launch_bounds__(64) void dmx_inflate_batch_kernel(const uint8_t* __
 // end_bit; a boundary beyond it, or BFINAL short of it, is -E_SZ, and so is an output that is not
 // out_len at the end.  The capacity is always the finite out_len + wlen: the symbol loop ends by
 // capacity, a block without output consumes input and the loop over blocks ends at end_bit, so every
-// loop here is bounded.  The one known cause of a run without end (the measure pass
-// with out_cap = UINT64_MAX behind a stream cut inside a block) needs an unbounded capacity and
-// cannot arise.  Long zero-run streams are not verified on the device (include/dmx.h).
+// loop here is bounded, and iblock's symbol loop also ends with the input (ib_past), whatever the
+// capacity.  Long zero-run streams (zlib's 4.2 MB blocks of two 1-bit codes) are in the GPU suite,
+// whole and by ranges (tests/test_gpu_refill.py; the refill they starved: isym_run's header).
 // ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void dmx_inflate_points_kernel(const uint8_t* __restrict__ z, uint64_t zbytes,
                                                                 const dmx_zpoint* __restrict__ points,

@@ -270,21 +270,30 @@
         "s_bfe_u32 s98, s99, 0x50008\n"
         "s_lshr_b64 s[94:95], s[94:95], s98\n"
         "s_sub_u32 %[bc], %[bc], s98\n"
-        // refill inside the token: the word is in vcur or vnxt
+        // refill inside the token: the word is in vcur, or it is the first of vnxt and the
+        // segments rotate here as at a token start.  Tokens of one size that divides 32 can put
+        // every refill of a long stretch here (zlib's zero runs: 2-bit tokens at odd offsets),
+        // so this site must rotate too: wi - wb never exceeds 64, and no read goes to a word
+        // at or behind wb + 128, which v_readlane would take modulo 64.  Where the run may not
+        // rotate (wb > wrl) the length is consumed and the distance is the caller's, refill
+        // included (IX_DIST): its ib_word rotates once, with guarded loads.
         "s_cmp_gt_u32 %[bc], 32\n"
         "s_cbranch_scc1 L_dl%=\n"
         "s_sub_u32 s98, %[wi], %[wb]\n"
         "s_cmp_lt_u32 s98, 64\n"
-        "s_cbranch_scc0 L_rn%=\n"
+        "s_cbranch_scc1 L_rm%=\n"
+        "s_cmp_le_i32 %[wb], %[wrl]\n"
+        "s_cbranch_scc0 L_xdist%=\n"
+        "s_waitcnt vmcnt(0)\n"
+        "v_mov_b32 %[vc], %[vn]\n"
+        "s_add_u32 %[wb], %[wb], 64\n"
+        "s_sub_u32 s98, s98, 64\n"
+        "s_add_u32 s99, %[wb], 64\n"
+        "v_add_lshl_u32 v114, %[lane], s99, 2\n"
+        "global_load_dword %[vn], v114, %[zb]\n"
+        "L_rm%=:\n"
         "s_nop 3\n"
         "v_readlane_b32 s96, %[vc], s98\n"
-        "s_branch L_rdd%=\n"
-        "L_rn%=:\n"
-        "s_sub_u32 s98, s98, 64\n"
-        "s_waitcnt vmcnt(0)\n"
-        "s_nop 3\n"
-        "v_readlane_b32 s96, %[vn], s98\n"
-        "L_rdd%=:\n"
         "s_lshl_b64 s[92:93], s[96:97], %[bc]\n"
         "s_or_b64 s[94:95], s[94:95], s[92:93]\n"
         "s_add_u32 %[wi], %[wi], 1\n"

@@ -768,8 +768,11 @@ int dmx_inflate_parallel_plan_host(const void* z, uint64_t zbytes, uint32_t fmt,
  * computed Adler-32; after an error the last three are 0.  d_status: dmx_batch_status over the
  * entries.  The capacity of an entry is always the finite out_len, so every loop ends by capacity or
  * by input.  Long zero-run streams (zlib's multi-megabyte blocks whose literal/length code is two
- * 1-bit codes) are indexed by the host builder but their device decode is unverified: two other
- * instantiations of the block decoder did not return on them, cause not found.
+ * 1-bit codes) decode like any other: up to 16 MiB of zeros at level 6, whole and by ranges, is in
+ * the GPU suite (tests/test_gpu_refill.py).  The runs that did not return on such streams had every
+ * refill of the bit reader between a length and its distance, where the reader's stream segments
+ * did not advance, so it re-read words it had consumed; that refill now advances them (DESIGN.md
+ * §3.1 "Equal-size tokens").
  * d_work: 256-byte aligned, work_bytes >= dmx_inflate_points_work(nsel) (= dmx_inflate_batch_work).
  * Returns before any device call: -E_INVAL (d_results, d_status, d_work NULL; d_points or d_windows
  * NULL with nsel > 0; d_z NULL with zbytes > 0; d_out NULL with nsel > 0; d_points, d_dst_off,

@@ -2,8 +2,7 @@
 zindex_read_ranges, zindex_pread): one foreign stream, indexed once on the host (zindex_build), decoded
 a wave per point.  Python's zlib gives the data; the index under test is the host builder's, which
 tests/test_zindex_api.py pins to zlib.  Every input is at most 1.5 MB decoded, every output buffer
-lies between canaries, and no stream here holds a long run of zeros (include/dmx.h: their device
-decode is unverified)."""
+lies between canaries.  Streams of long zero runs are in tests/test_gpu_refill.py."""
 import zlib
 
 import numpy as np
