@@ -17,6 +17,7 @@ include/dmx.h).  This module is a thin ctypes layer:
     inflate_batch(streams)                                many independent zlib / gzip / raw DEFLATE streams, side by side
                                                           (zdict=: preset dictionaries, zlib's FDICT / inflateSetDictionary)
     inflate_parallel_plan_host(z)                         ONE zlib / gzip / raw stream cut at true block starts (host)
+    inflate_parallel(zt)                                  ... cut on the device and decoded a wave per chunk, in one pass
     zindex_build(z) -> ZIndex                             ONE such stream indexed once on the host: seek points with windows
     inflate_indexed(zt, ix) / zindex_pread(zt, ix, off, n)  ... then decoded a wave per point, or only the points a range touches
     compress_batch(bufs)                                  many independent buffers into as many streams, in one chain of launches
@@ -43,6 +44,7 @@ __all__ = [
     "compress_batch", "compress_batch_async", "encode_batch_blocks", "EStream", "EResult", "EBatchStatus", "ERESULT_DTYPE",
     "compress_batch_dict_async",
     "inflate_parallel_plan_host", "PChunk", "ParStatus", "PCHUNK_DTYPE",
+    "inflate_parallel", "inflate_parallel_plan_async", "inflate_parallel_decode_async",
     "ZIndex", "ZIndexStatus", "zindex_build", "inflate_points_async", "inflate_indexed", "zindex_read_ranges", "zindex_pread",
     "DMX_ZINDEX_WINDOW", "DMX_ZINDEX_DEF_SPAN", "DMX_ZINDEX_MAX_SPAN",
 ]
@@ -260,6 +262,10 @@ def lib() -> ctypes.CDLL:
         "dmx_inflate_dict_host": ([vp, u64, u32, vp, u64, ctypes.POINTER(vp), ctypes.POINTER(u64), ctypes.POINTER(u64)],
                                   ctypes.c_int),
         "dmx_inflate_parallel_plan_host": ([vp, u64, u32, u32, vp, u32, ctypes.POINTER(ParStatus)], ctypes.c_int),
+        "dmx_inflate_parallel_plan_work": ([u64, u32], u64),
+        "dmx_inflate_parallel_plan_async": ([vp, u64, u32, u32, vp, u64, vp], ctypes.c_int),
+        "dmx_inflate_parallel_work": ([u64, u32], u64),
+        "dmx_inflate_parallel_decode_async": ([vp, u64, vp, u64, u32, vp, u64, vp, u64, ctypes.c_int, vp, vp], ctypes.c_int),
         "dmx_zindex_build_host": ([vp, u64, u32, u32, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
                                    ctypes.POINTER(ZIndexStatus)], ctypes.c_int),
         "dmx_inflate_points_work": ([u32], u64),
@@ -940,6 +946,90 @@ def inflate_parallel_plan_host(z, fmt: str = "auto", chunk_bytes: int | None = N
     del zk
     _check(r, "dmx_inflate_parallel_plan_host")
     return chunks, _par_info(rec)
+
+
+def inflate_parallel_plan_async(zt, fmt: int, chunk_bytes: int, plan, stream=None) -> int:
+    """dmx_inflate_parallel_plan_async on caller-owned CUDA tensors, enqueued on `stream` (the current
+    one by default) with no synchronisation, so it can be captured into a graph: zt the one stream's
+    bytes, fmt a DMX_BATCH_* format, chunk_bytes the cut (0: the default), plan a uint8 tensor of
+    lib().dmx_inflate_parallel_plan_work(zt.numel(), chunk_bytes) bytes (256-byte aligned) whose first
+    56 bytes receive the ParStatus record.  Returns the call's own return code."""
+    import torch
+    dev = plan.device
+    with torch.cuda.device(dev):
+        s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        return lib().dmx_inflate_parallel_plan_async(_ptr(zt), zt.numel() if zt is not None else 0, fmt, chunk_bytes,
+                                                     ctypes.c_void_p(plan.data_ptr()), plan.numel(), ctypes.c_void_p(s))
+
+
+def inflate_parallel_decode_async(zt, plan, max_live: int, out, out_cap: int, work, verify: bool, status, stream=None) -> int:
+    """dmx_inflate_parallel_decode_async on caller-owned CUDA tensors, as inflate_parallel_plan_async
+    (no synchronisation: both can be captured into one graph): plan as the plan call left it for zt,
+    max_live and out_cap the capacities, work a uint8 tensor of at least
+    lib().dmx_inflate_parallel_work(out_len, nlive) bytes (256-byte aligned), status a 56-byte tensor
+    (ParStatus).  Returns the call's own return code; the outcome is in the record."""
+    import torch
+    dev = work.device
+    with torch.cuda.device(dev):
+        s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        return lib().dmx_inflate_parallel_decode_async(_ptr(zt), zt.numel() if zt is not None else 0,
+                                                       ctypes.c_void_p(plan.data_ptr()), plan.numel(), max_live, _ptr(out),
+                                                       out_cap, ctypes.c_void_p(work.data_ptr()), work.numel(),
+                                                       1 if verify else 0, ctypes.c_void_p(status.data_ptr()),
+                                                       ctypes.c_void_p(s))
+
+
+def inflate_parallel(z, fmt: str = "auto", chunk_bytes: int | None = None, verify: bool = True, info: dict | None = None):
+    """One zlib stream, gzip member or raw DEFLATE stream that carries no index, decoded in one pass
+    on the GPU: z a contiguous uint8 CUDA tensor (or bytes, copied to the device here).  The plan
+    (dmx_inflate_parallel_plan_async) cuts it at true block starts, one synchronisation reads its
+    56-byte record, the output and the work buffer are allocated, and every live chunk decodes in a
+    wave of its own (dmx_inflate_parallel_decode_async).  Where the plan gave the stream up (a chunk
+    that expands beyond 4 MiB, too many false block starts) or found one chunk only (stored or fixed
+    blocks, nothing to cut), the stream takes the serial route: inflate_batch with that one stream.
+    verify: the Adler-32 / CRC-32 and ISIZE are checked on the device.  info (a dict) receives the
+    record's fields and route, "parallel" or "serial".  Returns a uint8 CUDA tensor; a stream with a
+    status raises DeflateError with it."""
+    import torch
+    if fmt not in _BATCH_FMT:
+        raise ValueError("fmt is one of " + ", ".join(_BATCH_FMT))
+    if isinstance(z, torch.Tensor):
+        if z.numel() and (z.dtype != torch.uint8 or not z.is_cuda or not z.is_contiguous()):
+            raise ValueError("inflate_parallel takes a contiguous uint8 CUDA tensor")
+        zt = z
+    else:
+        b = bytes(z)
+        zt = torch.frombuffer(bytearray(b or b"\0"), dtype=torch.uint8).cuda()[:len(b)]
+    L = lib()
+    dev = zt.device
+    cb = int(chunk_bytes or 0)
+    pb = int(L.dmx_inflate_parallel_plan_work(zt.numel(), cb))
+    if not pb:
+        raise ValueError("chunk_bytes is 1024 .. 2^30 (None or 0: the default), the stream at most 0xFFFFFFF0 bytes")
+    plan = torch.empty(pb, dtype=torch.uint8, device=dev)
+    _check(inflate_parallel_plan_async(zt, _BATCH_FMT[fmt], cb, plan), "dmx_inflate_parallel_plan_async")
+    rec = ParStatus.from_buffer_copy(plan[:56].cpu().numpy().tobytes())   # the call's one synchronisation before the decode
+    if info is not None:
+        info.update(_par_info(rec))
+        info["route"] = "parallel"
+    if rec.gave_up or (rec.status == 0 and rec.nlive == 1):
+        if info is not None:
+            info["route"] = "serial"
+        out, _, res = inflate_batch(zt, [(0, zt.numel())], fmt=fmt)
+        return out[:int(res["out_len"][0])]
+    if rec.status:
+        raise DeflateError(rec.status, "inflate_parallel")
+    out = torch.empty(max(rec.out_len, 1), dtype=torch.uint8, device=dev)
+    work = torch.empty(int(rec.work_len), dtype=torch.uint8, device=dev)
+    st = torch.empty(7, dtype=torch.int64, device=dev)
+    _check(inflate_parallel_decode_async(zt, plan, rec.nlive, out, rec.out_len, work, verify, st),
+           "dmx_inflate_parallel_decode_async")
+    rec = ParStatus.from_buffer_copy(st.cpu().numpy().tobytes())
+    if info is not None:
+        info.update(_par_info(rec))
+    if rec.status:
+        raise DeflateError(rec.status, "inflate_parallel")
+    return out[:rec.out_len]
 
 
 class ZIndex:

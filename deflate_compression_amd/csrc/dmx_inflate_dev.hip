@@ -33,6 +33,9 @@
 #include "../../include/dmx.h"
 #include "dmx_ctx.h"   // dmx_crc32_ranges_launch, dmx_crc32_batch_launch
 #include "dmx_gz_head.h"
+#include "dmx_pfind.h"   // the plan of one foreign stream: search, landing, walk, sizes
+#include "dmx_ptail.h"   // its decode: the tail and pack rules
+#include "dmx_crc.h"
 
 #define IW 32768          // window = LDS ring (stream mode; the indexed mode's ring is IWX)
 #ifndef DMX_IWX
@@ -1583,6 +1586,570 @@ extern "C" int dmx_inflate_points_async(const void* d_z, uint64_t zbytes, const 
     hipLaunchKernelGGL(dmx_inflate_points_kernel, dim3(grid), dim3(64), 0, s, (const uint8_t*)d_z, zbytes, d_points, d_adler,
                        (const uint8_t*)d_windows, npoints, d_sel, d_dst_off, nsel, (uint8_t*)d_out, out_bytes, d_results, gtab,
                        ctl, d_status);
+    return hipGetLastError() == hipSuccess ? 0 : -(int)E_DEVICE;
+}
+
+// ------------------------------------------------------------------------------------
+// One foreign stream in one pass (dmx_inflate_parallel_plan_async / _decode_async, include/dmx.h;
+// DESIGN.md 3.1 "One foreign stream: the decode").  The plan is dmx_inflate_parallel_plan_host's on
+// the device, four launches over d_plan = [head 256][live chunks 32 x nc][candidates 8 x nc]
+// [measures 32 x nc][tables 8 KiB x workgroups] (dmx_pf_plan_bytes):
+//   head     one thread: the framing (dmx_frame_head), the record's and the claim counter's reset
+//   find     a wave per chunk: the first bit offset of the chunk dmx_pf_valid accepts.  A step tests
+//            64 offsets: lanes 0..7 load the eight aligned words that hold them (whole words inside
+//            the stream, single bytes at its ends, zeros past it), every lane takes its two views
+//            from them by cross-lane reads, dmx_pf_filter_w runs on all 64, dmx_pf_header only in
+//            the lanes the filter left, and the lowest accepted lane ends the search
+//   measure  workgroups of one wave claim candidates from the counter and decode them for lengths
+//            only (iblock without stores, the window taken as primed, capacity
+//            DMX_PF_MAX_CHUNK_OUT + 1, the reader bounded by the input: every loop ends), with dmx_pf_land at every block boundary.  Every
+//            candidate is measured, not only those the walk reaches: a dead one costs time, and
+//            its record is never read
+//   link     one thread: dmx_pf_link, the walk that keeps the live chunks, and the trailer
+// The decode, over d_work = [control 256][tables 8 KiB x workgroups][cells 2 x out_len][piece index,
+// unused][piece CRC-32 remainders 4 x np][piece Adler-32 sums 4 x np] (dmx_pf_work; every offset is
+// computed on the device from the record's out_len and nlive):
+//   begin    one thread: the plan's record into d_status, the capacity checks (-E_SZ), the reset
+//   cells    a wave per live chunk, claimed from a counter: iblock into 16-bit cells (CELL) with
+//            base = out_off and cap = out_len until exactly end_bit
+//   tails    one workgroup of 1 024 threads walks the live chunks in order with the 32 KiB in front
+//            of the current chunk in LDS (dmx_ptail.h)
+//   pack     cells into bytes; what is still a reference reads a cell the tail pass resolved
+//   check    (verify) per piece of 64 KiB the Adler-32 sums or the raw CRC-32 remainder
+//   status   one thread: the first error by chunk order, the pieces combined, the trailer compared
+// A workgroup beyond the device-side counts leaves at once; after a status no later stage runs.
+// ------------------------------------------------------------------------------------
+struct PPlanHead {   // the first 256 bytes of d_plan
+    dmx_par_status st;         // 0: the record
+    uint32_t chunk_bytes;      // 56
+    uint32_t isize;            // 60: gzip's ISIZE
+    uint64_t body_bit;         // 64
+    uint64_t zbytes;           // 72
+    unsigned long long next;   // 80: the measure pass's claim counter
+};
+static_assert(sizeof(dmx_par_status) == 56 && sizeof(PPlanHead) <= 256 && sizeof(dmx_pf_meas) == 32, "d_plan's layout");
+
+struct PDecCtl {   // the first 256 bytes of d_work
+    unsigned long long next;   // the cell pass's claim counter
+    unsigned long long err;    // chunk << 32 | status, an integer minimum: the first chunk's error
+    uint64_t out_len;
+    uint32_t go, nlive, format, check, isize;
+};
+#define PDEC_NOERR (~0ull)
+__device__ __forceinline__ void pdec_fail(PDecCtl* ctl, uint32_t chunk, int err) {
+    atomicMin(&ctl->err, ((unsigned long long)chunk << 32) | (uint32_t)err);
+}
+__device__ __forceinline__ uint8_t* pdec_cells(uint8_t* work, uint32_t nlive) { return work + 256 + 8192 * dmx_pf_cell_wg(nlive); }
+__device__ __forceinline__ uint32_t* pdec_crcs(uint8_t* work, uint64_t out_len, uint32_t nlive) {
+    const uint64_t np = dmx_pf_pieces(out_len);
+    return (uint32_t*)(pdec_cells(work, nlive) + dmx_pf_a256(2 * out_len) + dmx_pf_a256(24 * np));
+}
+
+__global__ void dmx_par_head_kernel(const uint8_t* __restrict__ z, uint64_t zbytes, uint32_t fmt, uint32_t chunk,
+                                    uint32_t nc, PPlanHead* __restrict__ h, uint64_t* __restrict__ cand) {
+    dmx_par_status st;
+    uint64_t body = 0;
+    uint32_t format = 0;
+    st.status = dmx_frame_head(z, zbytes, fmt, &format, &body);
+    st.format = format;
+    st.out_len = st.in_used = st.work_len = 0;
+    st.check = st.nlive = st.ndead = st.gave_up = 0;
+    st.nchunks = nc;
+    st.ncand = st.status ? 0u : 1u;
+    h->st = st;
+    h->chunk_bytes = chunk;
+    h->isize = 0;
+    h->body_bit = 8 * body;
+    h->zbytes = zbytes;
+    h->next = 0;
+    cand[0] = 8 * body;
+}
+
+// word wi of the aligned view of z (zb = z rounded down to 4 bytes; the stream is bytes [mis, end)
+// of it): a whole word inside the stream is one load, any other is assembled from the stream's bytes
+__device__ __forceinline__ uint32_t par_word(const uint8_t* zb, uint32_t mis, uint64_t end, uint64_t wi) {
+    if (4 * wi + 4 <= end) return reinterpret_cast<const uint32_t*>(zb)[wi];   // (the first may begin up to 3 bytes in front)
+    uint32_t v = 0;
+    for (uint32_t j = 0; j < 4; j++) {
+        const uint64_t b = 4 * wi + j;
+        if (b >= mis && b < end) v |= (uint32_t)zb[b] << (8 * j);
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(64) void dmx_par_find_kernel(const uint8_t* __restrict__ z, uint64_t zbytes,
+                                                          PPlanHead* __restrict__ h, uint64_t* __restrict__ cand) {
+    const uint32_t c = blockIdx.x, lane = threadIdx.x;
+    if (c == 0 || h->st.status) return;   // chunk 0 begins at the framing's bit
+    uint64_t lo, hi;
+    dmx_pf_range(c, h->chunk_bytes, zbytes, h->body_bit, &lo, &hi);
+    const uintptr_t a = (uintptr_t)z;
+    const uint8_t* zb = (const uint8_t*)(a & ~(uintptr_t)3);
+    const uint32_t mis = (uint32_t)(a & 3);
+    const uint64_t end = mis + zbytes;
+    uint64_t found = DMX_PF_NONE;
+    for (uint64_t b0 = lo; b0 < hi; b0 += 64) {
+        const uint64_t w0 = ((b0 >> 3) + mis) >> 2;   // the first staged word
+        const uint32_t wv = lane < 8 ? par_word(zb, mis, end, w0 + lane) : 0u;
+        const uint64_t bit = b0 + lane;
+        // the lane's 16 bytes begin rb <= 3 + 8 bytes into the staged words: words k .. k + 4, k <= 2
+        const uint32_t rb = (uint32_t)(((bit >> 3) + mis) - 4 * w0), k = rb >> 2, sh = 8 * (rb & 3);
+        uint32_t x[5];
+#pragma unroll
+        for (int q = 0; q < 5; q++) x[q] = (uint32_t)__shfl((int)wv, (int)(k + q), 64);
+        uint32_t y[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) y[q] = (uint32_t)((((uint64_t)x[q + 1] << 32) | x[q]) >> sh);
+        const uint64_t L = ((uint64_t)y[1] << 32) | y[0], H = ((uint64_t)y[3] << 32) | y[2];   // bytes p .. p + 7, p + 8 .. p + 15
+        const uint32_t s = (uint32_t)bit & 7;
+        const uint64_t w = L >> s, w2 = ((L >> 56) | (H << 8)) >> s;   // dmx_pf_peek at bit and at bit + 56
+        uint64_t cl = 0;
+        uint32_t hdr = 0;
+        const bool pass = bit < hi && dmx_pf_filter_w(w, w2, zbytes, bit, &cl, &hdr);
+        bool ok = false;
+        if (__ballot(pass)) ok = pass && dmx_pf_header(z, zbytes, bit, cl, hdr);
+        const uint64_t am = __ballot(ok);
+        if (am) {
+            found = b0 + (uint32_t)__builtin_ctzll(am);
+            break;
+        }
+    }
+    if (lane == 0) {
+        cand[c] = found;
+        if (found != DMX_PF_NONE) atomicAdd(&h->st.ncand, 1u);
+    }
+}
+
+__global__ __launch_bounds__(64) void dmx_par_measure_kernel(const uint8_t* __restrict__ z, uint64_t zbytes,
+                                                             PPlanHead* __restrict__ h, const uint64_t* __restrict__ cand,
+                                                             dmx_pf_meas* __restrict__ meas, uint32_t nc,
+                                                             uint32_t* __restrict__ gtab) {
+    __shared__ InfLDS<IW> S;   // the kernel's one __shared__ object: isym_run addresses the ring from LDS 0
+    if (h->st.status) return;
+    uint32_t* gt = gtab + (uint64_t)blockIdx.x * ITAB_WORDS;
+    const uint32_t lane = threadIdx.x;
+    for (;;) {
+        unsigned long long claim = 0;
+        if (lane == 0) claim = atomicAdd(&h->next, 1ull);
+        const uint64_t k64 = rfl64(claim);
+        if (k64 >= nc) break;
+        const uint32_t k = (uint32_t)k64;
+        const uint64_t start = rfl64(cand[k]);
+        if (start == DMX_PF_NONE) continue;
+        IBits r;
+        IOut o;
+#ifdef DMX_INF_STAMPS
+        for (int q = 0; q < INF_NST; q++) o.st[q] = 0;
+#endif
+        // The window is taken as primed, as a preset dictionary of IW bytes primes it (the arithmetic
+        // above IBatchDict) but without its bytes: nothing is stored and only lengths count, so no
+        // distance is too far here -- chunk 0's included, as on the host: a distance before the
+        // first output byte is the decode's to find.
+        o.out = nullptr;
+        o.base = 0;
+        o.ob = 0;
+        o.cap = DMX_PF_MAX_CHUNK_OUT + 1 + IW;
+        o.op = IW;
+        o.fl = IW;
+        o.a = 1;
+        o.b = 0;
+        ib_init(r, z, zbytes);
+        ib_seek(r, start);
+        uint32_t t = k + 1, skipped = 0, flags = 0, next = 0xFFFFFFFFu;
+        int status = 0;
+        uint64_t out_len = 0;
+        for (;;) {
+            bool last = false;
+            const int e = ib_status(r, iblock<true, true, IW, false, false>(S, r, o, gt, lane, last));
+            status = (int)rfl((uint32_t)e);
+            out_len = rfl64(o.ob + o.op - IW);
+            if (status == -(int)E_SZ || (!status && out_len > DMX_PF_MAX_CHUNK_OUT)) {   // too much for one chunk
+                status = 0;
+                flags = DMX_PF_LOST;
+                break;
+            }
+            if (status) break;
+            if (rfl(last ? 1u : 0u)) {
+                flags = DMX_PF_LAST;
+                break;
+            }
+            const uint64_t pos = (uint64_t)rfl(r.wi) * 32 - rfl(r.bc) - 8ull * r.lo;
+            const int ld = (int)rfl((uint32_t)dmx_pf_land(cand, nc, &t, pos, &skipped));
+            t = rfl(t);
+            skipped = rfl(skipped);
+            if (ld == 1) {
+                next = t;
+                break;
+            }
+            if (ld == 2) {
+                flags = DMX_PF_LOST;
+                break;
+            }
+        }
+        if (lane == 0) {
+            dmx_pf_meas m;
+            m.end_bit = (uint64_t)rfl(r.wi) * 32 - rfl(r.bc) - 8ull * r.lo;
+            m.out_len = out_len;
+            m.next = next;
+            m.flags = flags;
+            m.status = status;
+            m.reserved = 0;
+            meas[k] = m;
+        }
+        __syncthreads();   // the ring and the small arrays are the next candidate's
+    }
+}
+
+__global__ void dmx_par_link_kernel(const uint8_t* __restrict__ z, uint64_t zbytes, PPlanHead* __restrict__ h,
+                                    const uint64_t* __restrict__ cand, const dmx_pf_meas* __restrict__ meas,
+                                    dmx_pchunk* __restrict__ chunks, uint32_t nc) {
+    if (h->st.status) return;
+    dmx_par_status st = h->st;
+    uint32_t isize = 0;
+    dmx_pf_link(z, zbytes, cand, meas, chunks, nc, &st, &isize);
+    h->st = st;
+    h->isize = isize;
+}
+
+__global__ void dmx_par_begin_kernel(const PPlanHead* __restrict__ h, uint64_t plan_bytes, uint64_t zbytes, uint32_t max_live,
+                                     uint64_t out_cap, uint64_t work_bytes, PDecCtl* __restrict__ ctl,
+                                     dmx_par_status* __restrict__ d_status) {
+    dmx_par_status st = h->st;
+    ctl->next = 0;
+    ctl->err = PDEC_NOERR;
+    ctl->go = 0;
+    if (!st.status) {
+        // a plan of other bytes, or no plan at all: nothing below may trust its numbers
+        if (h->zbytes != zbytes || !st.nlive || st.nlive > st.nchunks || plan_bytes < dmx_pf_plan_bytes(st.nchunks) ||
+            st.out_len > DMX_PF_MAX_POS) {
+            st.status = -(int32_t)E_INVAL;
+            st.out_len = st.in_used = st.work_len = 0;
+            st.check = 0;
+        } else if (st.nlive > max_live || st.out_len > out_cap || work_bytes < dmx_pf_work(st.out_len, st.nlive)) {
+            st.status = -(int32_t)E_SZ;   // the record holds the needed numbers
+        } else {
+            ctl->out_len = st.out_len;
+            ctl->nlive = st.nlive;
+            ctl->format = st.format;
+            ctl->check = st.check;
+            ctl->isize = h->isize;
+            ctl->go = 1;
+        }
+    }
+    *d_status = st;
+}
+
+__global__ __launch_bounds__(64) void dmx_par_cells_kernel(const uint8_t* __restrict__ z, uint64_t zbytes,
+                                                           const dmx_pchunk* __restrict__ chunks, uint8_t* __restrict__ work,
+                                                           PDecCtl* __restrict__ ctl) {
+    __shared__ InfLDS<IWC, uint16_t> S;   // the kernel's one __shared__ object
+    if (!ctl->go) return;
+    const uint32_t nlive = ctl->nlive;
+    if (blockIdx.x >= dmx_pf_cell_wg(nlive)) return;   // (no table area of its own)
+    const uint64_t total = ctl->out_len;
+    uint32_t* gt = (uint32_t*)(work + 256) + (uint64_t)blockIdx.x * ITAB_WORDS;
+    uint8_t* cells = pdec_cells(work, nlive);
+    const uint32_t lane = threadIdx.x;
+    for (;;) {
+        unsigned long long claim = 0;
+        if (lane == 0) claim = atomicAdd(&ctl->next, 1ull);
+        const uint64_t i64 = rfl64(claim);
+        if (i64 >= nlive) break;
+        const uint32_t i = (uint32_t)i64;
+        const uint64_t bit = rfl64(chunks[i].bit), end_bit = rfl64(chunks[i].end_bit);
+        const uint64_t off = rfl64(chunks[i].out_off), olen = rfl64(chunks[i].out_len);
+        const uint64_t nxt = i + 1 < nlive ? rfl64(chunks[i + 1].out_off) : total;
+        int err = 0;
+        // the chunks tile [0, out_len) in order: the tail and pack passes rely on it
+        if (bit >= end_bit || end_bit > 8 * zbytes || olen > DMX_PF_MAX_CHUNK_OUT || off > total || olen > total - off ||
+            off + olen != nxt || (i == 0 && off != 0))
+            err = -(int)E_RANGE;
+        IBits r;
+        IOut o;
+#ifdef DMX_INF_STAMPS
+        for (int q = 0; q < INF_NST; q++) o.st[q] = 0;
+#endif
+        o.out = cells;
+        o.base = off;
+        o.ob = 0;
+        o.cap = olen;
+        o.op = 0;
+        o.fl = 0;
+        o.a = 1;
+        o.b = 0;
+        if (!err) {
+            ib_init(r, z, zbytes);
+            ib_seek(r, bit);
+            for (;;) {   // blocks until exactly end_bit, by the seek-point kernel's rules
+                bool last = false;
+                const int e = ib_status(r, iblock<true, false, IWC, true>(S, r, o, gt, lane, last));
+                err = (int)rfl((uint32_t)e);
+                if (err) break;
+                const uint64_t used = (uint64_t)rfl(r.wi) * 32 - rfl(r.bc) - 8ull * r.lo;
+                if (used == end_bit) break;
+                if (used > end_bit || rfl(last ? 1u : 0u)) { err = -(int)E_SZ; break; }
+            }
+        }
+        if (!err && o.ob + o.op != olen) err = -(int)E_SZ;
+        if (!err) io_flush<false>(S, o, o.op, lane);
+        if (err && lane == 0) pdec_fail(ctl, i, err);
+        __syncthreads();   // the ring and the small arrays are the next chunk's
+    }
+}
+
+#define PTAIL_T 1024u
+#define PTAIL_Q (DMX_PT_WIN / PTAIL_T)   // window positions per thread
+__global__ __launch_bounds__(PTAIL_T) void dmx_par_tails_kernel(const dmx_pchunk* __restrict__ chunks,
+                                                                uint8_t* __restrict__ work, PDecCtl* __restrict__ ctl) {
+    // two windows, not one ring: a reference is relative to the chunk's start, so any cell of a long
+    // chunk's tail may name any of the 32 768 positions before the chunk
+    __shared__ uint8_t win[2][DMX_PT_WIN];
+    if (!ctl->go || ctl->err != PDEC_NOERR) return;
+    const uint32_t nlive = ctl->nlive, tid = threadIdx.x;
+    uint16_t* cells = reinterpret_cast<uint16_t*>(pdec_cells(work, nlive));
+    uint32_t cur = 0, bad = 0xFFFFFFFFu;
+    for (uint32_t i = 0; i < nlive; i++) {
+        const uint64_t off = chunks[i].out_off, len = chunks[i].out_len;
+        uint16_t* tc = cells + off + len - dmx_pt_tail(len);   // the tail's cells
+        const uint8_t* W = win[cur];
+        uint8_t* N = win[cur ^ 1];
+        // window position k = tid + PTAIL_T q of the next window: a tail entry or an old byte
+        uint16_t c[PTAIL_Q];
+#pragma unroll
+        for (uint32_t q = 0; q < PTAIL_Q; q++) {   // all loads first: they fly together
+            uint32_t idx;
+            c[q] = dmx_pt_next(tid + PTAIL_T * q, len, &idx) ? tc[idx] : (uint16_t)0;
+        }
+#pragma unroll
+        for (uint32_t q = 0; q < PTAIL_Q; q++) {
+            uint32_t idx;
+            int v;
+            if (dmx_pt_next(tid + PTAIL_T * q, len, &idx)) {
+                v = dmx_pt_cell(c[q], W, off);
+                if (v < 0) {
+                    bad = bad < i ? bad : i;
+                    v = 0;
+                }
+                tc[idx] = (uint16_t)v;   // the byte, in place
+            } else {
+                v = W[idx];
+            }
+            N[tid + PTAIL_T * q] = (uint8_t)v;
+        }
+        __syncthreads();
+        cur ^= 1;
+    }
+    if (bad != 0xFFFFFFFFu) pdec_fail(ctl, bad, -(int)E_HUFDIS);   // before output offset 0
+}
+
+#define PPACK_T 256u
+#define PPACK_MAX_WG 4096u
+__global__ __launch_bounds__(PPACK_T) void dmx_par_pack_kernel(const dmx_pchunk* __restrict__ chunks,
+                                                               uint8_t* __restrict__ work, PDecCtl* __restrict__ ctl,
+                                                               uint8_t* __restrict__ out) {
+    if (!ctl->go || ctl->err != PDEC_NOERR) return;
+    const uint32_t nlive = ctl->nlive;
+    const uint64_t n = ctl->out_len;   // <= out_cap (begin)
+    const uint16_t* cells = reinterpret_cast<const uint16_t*>(pdec_cells(work, nlive));
+    for (uint64_t q = 4 * ((uint64_t)blockIdx.x * PPACK_T + threadIdx.x); q < n; q += 4ull * PPACK_T * gridDim.x) {
+        uint32_t lo = 0, hi = nlive;   // the last chunk that begins at or before q
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (chunks[mid].out_off <= q) lo = mid;
+            else hi = mid;
+        }
+        uint32_t i = lo;
+        uint64_t off = chunks[i].out_off, end = off + chunks[i].out_len;
+        uint32_t b4 = 0;
+        const uint32_t m = n - q < 4 ? (uint32_t)(n - q) : 4u;
+        for (uint32_t j = 0; j < m; j++) {
+            const uint64_t p = q + j;
+            while (p >= end && i + 1 < nlive) {
+                i++;
+                off = chunks[i].out_off;
+                end = off + chunks[i].out_len;
+            }
+            int v = dmx_pt_pack(cells, p, off);
+            if (v < 0) {
+                pdec_fail(ctl, i, -(int)E_HUFDIS);
+                v = 0;
+            }
+            b4 |= (uint32_t)v << (8 * j);
+        }
+        if (m == 4 && (((uintptr_t)out + q) & 3) == 0) {
+            *reinterpret_cast<uint32_t*>(out + q) = b4;
+        } else {
+            for (uint32_t j = 0; j < m; j++) out[q + j] = (uint8_t)(b4 >> (8 * j));
+        }
+    }
+}
+
+// Per piece of DMX_PF_PIECE bytes of the packed output: zlib, the sums (a, b) of the piece from
+// a = b = 0 with position weights (io_flush's fold: b counts a byte once for every byte from it to
+// the piece's end), packed b << 16 | a; gzip, the piece's raw CRC-32 remainder (dmx_crc.h).  A thread
+// takes 256 bytes; the slices combine by the same rules.
+#define PCHK_T 256u
+#define PCHK_MAX_WG 2048u
+static_assert(PCHK_T * 256u == DMX_PF_PIECE, "a thread's slice");
+__global__ __launch_bounds__(PCHK_T) void dmx_par_check_kernel(const uint8_t* __restrict__ out, uint8_t* __restrict__ work,
+                                                               PDecCtl* __restrict__ ctl) {
+    __shared__ uint32_t tab[256];
+    __shared__ uint32_t ra[PCHK_T], rb[PCHK_T];
+    if (!ctl->go || ctl->err != PDEC_NOERR || ctl->format == DMX_BATCH_RAW) return;
+    constexpr uint32_t M = 65521u;
+    const bool gz = ctl->format == DMX_BATCH_GZIP;
+    const uint64_t n = ctl->out_len, np = dmx_pf_pieces(n);
+    uint32_t* crcs = pdec_crcs(work, n, ctl->nlive);
+    uint32_t* adls = crcs + dmx_pf_a256(4 * np) / 4;
+    const uint32_t tid = threadIdx.x;
+    uint32_t e = tid;
+    for (int k = 0; k < 8; k++) e = (e >> 1) ^ ((0u - (e & 1u)) & DMX_CRC_POLY);
+    tab[tid] = e;
+    const uint32_t xfull = gz ? dmx_gf2_xpow((uint64_t)(PCHK_T - 1 - tid) * 256, 3) : 0u;   // the bytes behind the slice in a full piece
+    __syncthreads();
+    for (uint64_t pc = blockIdx.x; pc < np; pc += gridDim.x) {
+        const uint64_t lo = pc * DMX_PF_PIECE, hi = n - lo < DMX_PF_PIECE ? n : lo + DMX_PF_PIECE;
+        const uint64_t s0 = lo + 256ull * tid < hi ? lo + 256ull * tid : hi, s1 = hi - s0 < 256 ? hi : s0 + 256;
+        uint32_t va = 0, vb = 0;
+        if (gz) {
+            uint32_t r = 0;
+            for (uint64_t p = s0; p < s1; p++) r = tab[(r ^ out[p]) & 255u] ^ (r >> 8);
+            if (s0 < s1) va = dmx_gf2_mulmod(r, hi - lo == DMX_PF_PIECE ? xfull : dmx_gf2_xpow(hi - s1, 3));
+        } else {
+            uint32_t sa = 0;
+            uint64_t sb = 0;   // <= 256 x 65 536 x 255
+            for (uint64_t p = s0; p < s1; p++) {
+                const uint32_t x = out[p];
+                sa += x;
+                sb += (hi - p) * x;
+            }
+            va = sa;
+            vb = (uint32_t)(sb % M);
+        }
+        ra[tid] = va;
+        rb[tid] = vb;
+        __syncthreads();
+        if (tid == 0) {
+            if (gz) {
+                uint32_t r = 0;
+                for (uint32_t k = 0; k < PCHK_T; k++) r ^= ra[k];
+                crcs[pc] = r;
+            } else {
+                uint64_t A = 0, B = 0;
+                for (uint32_t k = 0; k < PCHK_T; k++) { A += ra[k]; B += rb[k]; }
+                adls[pc] = ((uint32_t)(B % M) << 16) | (uint32_t)(A % M);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+__global__ void dmx_par_status_kernel(uint8_t* __restrict__ work, PDecCtl* __restrict__ ctl, int verify,
+                                      dmx_par_status* __restrict__ st) {
+    if (!ctl->go) return;   // the plan's status, -E_INVAL or -E_SZ: begin wrote it
+    int err = ctl->err != PDEC_NOERR ? (int)(uint32_t)(ctl->err & 0xFFFFFFFFull) : 0;
+    const uint64_t n = ctl->out_len, np = dmx_pf_pieces(n);
+    if (!err && verify && ctl->format != DMX_BATCH_RAW) {
+        const uint32_t* crcs = pdec_crcs(work, n, ctl->nlive);
+        const uint32_t* adls = crcs + dmx_pf_a256(4 * np) / 4;
+        if (ctl->format == DMX_BATCH_ZLIB) {
+            constexpr uint64_t M = 65521u;
+            uint64_t a = 1, b = 0;
+            for (uint64_t pc = 0; pc < np; pc++) {   // a' = a + S, b' = b + len a + T
+                const uint64_t len = pc + 1 < np ? DMX_PF_PIECE : n - pc * DMX_PF_PIECE;
+                b = (b + (len % M) * a + (adls[pc] >> 16)) % M;
+                a = (a + (adls[pc] & 0xFFFFu)) % M;
+            }
+            if ((uint32_t)((b << 16) | a) != ctl->check) err = -(int)E_ZADL32;
+        } else {
+            const uint32_t xp = dmx_gf2_xpow(DMX_PF_PIECE, 3);
+            uint32_t r = 0;
+            for (uint64_t pc = 0; pc < np; pc++) {   // R(A || B) = R(A) x^(8 |B|) xor R(B)
+                const uint64_t len = pc + 1 < np ? DMX_PF_PIECE : n - pc * DMX_PF_PIECE;
+                r = dmx_gf2_mulmod(r, len == DMX_PF_PIECE ? xp : dmx_gf2_xpow(len, 3)) ^ crcs[pc];
+            }
+            if ((r ^ dmx_crc32_affine(n)) != ctl->check) err = -(int)E_CRC;
+            else if (ctl->isize != (uint32_t)n) err = -(int)E_LEN;
+        }
+    }
+    if (err) {
+        st->status = err;
+        st->out_len = 0;
+        st->in_used = 0;
+        st->check = 0;
+        st->work_len = 0;
+    }
+}
+
+static inline uint32_t par_chunk(uint32_t chunk_bytes) { return chunk_bytes ? chunk_bytes : DMX_PF_DEF_CHUNK; }
+
+extern "C" uint64_t dmx_inflate_parallel_plan_work(uint64_t zbytes, uint32_t chunk_bytes) {
+    const uint32_t chunk = par_chunk(chunk_bytes);
+    if (chunk < DMX_PF_MIN_CHUNK || chunk > DMX_PF_MAX_CHUNK || zbytes > DMX_PF_MAX_POS) return 0;
+    return dmx_pf_plan_bytes(dmx_pf_nchunks(zbytes, chunk));
+}
+
+extern "C" int dmx_inflate_parallel_plan_async(const void* d_z, uint64_t zbytes, uint32_t fmt, uint32_t chunk_bytes,
+                                               void* d_plan, uint64_t plan_bytes, void* stream) {
+    if (!d_plan || (!d_z && zbytes) || fmt > DMX_BATCH_RAW || ((uintptr_t)d_plan & 255)) return -(int)E_INVAL;
+    const uint32_t chunk = par_chunk(chunk_bytes);
+    if (chunk < DMX_PF_MIN_CHUNK || chunk > DMX_PF_MAX_CHUNK) return -(int)E_INVAL;
+    if (zbytes > DMX_PF_MAX_POS) return -(int)E_RANGE;
+    const uint32_t nc = dmx_pf_nchunks(zbytes, chunk);
+    if (plan_bytes < dmx_pf_plan_bytes(nc)) return -(int)E_INVAL;
+    hipStream_t s = (hipStream_t)stream;
+    uint8_t* P = (uint8_t*)d_plan;
+    PPlanHead* h = (PPlanHead*)P;
+    dmx_pchunk* chunks = (dmx_pchunk*)(P + 256);
+    uint64_t* cand = (uint64_t*)(P + 256 + dmx_pf_a256(32ull * nc));
+    dmx_pf_meas* meas = (dmx_pf_meas*)((uint8_t*)cand + dmx_pf_a256(8ull * nc));
+    uint32_t* gtab = (uint32_t*)((uint8_t*)meas + dmx_pf_a256(32ull * nc));
+    const uint8_t* z = (const uint8_t*)d_z;
+    hipLaunchKernelGGL(dmx_par_head_kernel, dim3(1), dim3(1), 0, s, z, zbytes, fmt, chunk, nc, h, cand);
+    if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
+    hipLaunchKernelGGL(dmx_par_find_kernel, dim3(nc), dim3(64), 0, s, z, zbytes, h, cand);
+    if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
+    hipLaunchKernelGGL(dmx_par_measure_kernel, dim3((uint32_t)dmx_pf_meas_wg(nc)), dim3(64), 0, s, z, zbytes, h, cand, meas, nc,
+                       gtab);
+    if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
+    hipLaunchKernelGGL(dmx_par_link_kernel, dim3(1), dim3(1), 0, s, z, zbytes, h, cand, meas, chunks, nc);
+    return hipGetLastError() == hipSuccess ? 0 : -(int)E_DEVICE;
+}
+
+extern "C" uint64_t dmx_inflate_parallel_work(uint64_t out_cap, uint32_t max_live) { return dmx_pf_work(out_cap, max_live); }
+
+extern "C" int dmx_inflate_parallel_decode_async(const void* d_z, uint64_t zbytes, const void* d_plan, uint64_t plan_bytes,
+                                                 uint32_t max_live, void* d_out, uint64_t out_cap, void* d_work,
+                                                 uint64_t work_bytes, int verify, dmx_par_status* d_status, void* stream) {
+    if (!d_plan || !d_work || !d_status || (!d_z && zbytes) || (!d_out && out_cap)) return -(int)E_INVAL;
+    if (((uintptr_t)d_plan & 255) || ((uintptr_t)d_work & 255) || ((uintptr_t)d_status & 7)) return -(int)E_INVAL;
+    if (plan_bytes < dmx_pf_plan_bytes(1) || work_bytes < 256) return -(int)E_INVAL;
+    if (zbytes > DMX_PF_MAX_POS) return -(int)E_RANGE;
+    hipStream_t s = (hipStream_t)stream;
+    const PPlanHead* h = (const PPlanHead*)d_plan;
+    const dmx_pchunk* chunks = (const dmx_pchunk*)((const uint8_t*)d_plan + 256);
+    uint8_t* work = (uint8_t*)d_work;
+    PDecCtl* ctl = (PDecCtl*)work;
+    const uint8_t* z = (const uint8_t*)d_z;
+    hipLaunchKernelGGL(dmx_par_begin_kernel, dim3(1), dim3(1), 0, s, h, plan_bytes, zbytes, max_live, out_cap, work_bytes, ctl,
+                       d_status);
+    if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
+    hipLaunchKernelGGL(dmx_par_cells_kernel, dim3((uint32_t)dmx_pf_cell_wg(max_live)), dim3(64), 0, s, z, zbytes, chunks, work,
+                       ctl);
+    if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
+    hipLaunchKernelGGL(dmx_par_tails_kernel, dim3(1), dim3(PTAIL_T), 0, s, chunks, work, ctl);
+    if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
+    const uint64_t pw = (out_cap + 4 * PPACK_T - 1) / (4 * PPACK_T);
+    hipLaunchKernelGGL(dmx_par_pack_kernel, dim3(pw < PPACK_MAX_WG ? (pw ? (uint32_t)pw : 1u) : PPACK_MAX_WG), dim3(PPACK_T), 0, s,
+                       chunks, work, ctl, (uint8_t*)d_out);
+    if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
+    if (verify) {
+        const uint64_t np = dmx_pf_pieces(out_cap);
+        hipLaunchKernelGGL(dmx_par_check_kernel, dim3(np < PCHK_MAX_WG ? (uint32_t)np : PCHK_MAX_WG), dim3(PCHK_T), 0, s,
+                           (const uint8_t*)d_out, work, ctl);
+        if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
+    }
+    hipLaunchKernelGGL(dmx_par_status_kernel, dim3(1), dim3(1), 0, s, work, ctl, verify, d_status);
     return hipGetLastError() == hipSuccess ? 0 : -(int)E_DEVICE;
 }
 

@@ -2,9 +2,10 @@
 // (dmx_inflate_parallel_plan_host, include/dmx.h; DESIGN.md 3.1 "One foreign stream"): the test
 // whether a bit offset may be the start of a non-final dynamic block, the step from a block
 // boundary to the next candidate, and the walk that keeps the chunks the stream really passes
-// through.  One text for the host plan (dmx_inflate_par_host.cpp) and the model under the
-// sanitizers (tests/c/pfind_model.cpp); it is written to compile for the device as well (no
-// arrays that need scratch, no table build), where a lane tests an offset.  C++ only, internal.
+// through.  One text for the host plan (dmx_inflate_par_host.cpp), the model under the
+// sanitizers (tests/c/pfind_model.cpp) and the device plan (dmx_inflate_parallel_plan_async,
+// dmx_inflate_dev.hip: no arrays that need scratch, no table build), where a lane tests an
+// offset.  C++ only, internal.
 #ifndef DMX_PFIND_H
 #define DMX_PFIND_H
 
@@ -58,8 +59,9 @@ static inline DMX_PF_HD uint32_t dmx_pf_nchunks(uint64_t zbytes, uint32_t chunk_
     return n ? (uint32_t)n : 1u;
 }
 
-// d_work of the decode: [control 256][tables 8 KiB x workgroups][cells 2 x out_len][piece index 24 x np]
-// [piece CRC-32s 4 x np][piece Adler-32s 4 x np], every part 256-byte aligned
+// d_work of the decode: [control 256][tables 8 KiB x workgroups][cells 2 x out_len][piece index 24 x np,
+// reserved: the check computes its pieces' ranges itself][piece CRC-32 remainders 4 x np][piece
+// Adler-32 sums 4 x np], every part 256-byte aligned
 static inline DMX_PF_HD uint64_t dmx_pf_pieces(uint64_t out_len) {
     const uint64_t np = (out_len + DMX_PF_PIECE - 1) / DMX_PF_PIECE;
     return np ? np : 1;
@@ -96,18 +98,19 @@ static inline DMX_PF_HD uint64_t dmx_pf_peek(const uint8_t* z, uint64_t n, uint6
 // The cheap filter: BFINAL = 0, BTYPE = 2, HLIT <= 29, HDIST <= 29, the code length code exactly
 // complete (Kraft sum of its up to 19 three-bit lengths), and the header so far inside the input.
 // *clp receives the 19 lengths, three bits each at 3 x symbol; *hdr the 17 header bits.
-static inline DMX_PF_HD bool dmx_pf_filter(const uint8_t* z, uint64_t n, uint64_t bit, uint64_t* clp, uint32_t* hdr) {
-    const uint64_t w = dmx_pf_peek(z, n, bit);
+// dmx_pf_filter_w is the filter on bits the caller holds -- w the bits from `bit` on (57 at least),
+// w2 those from bit + 56 on (18 at least; looked at only where the code length code has more than 13
+// lengths): the device search stages its chunk as aligned words and hands every lane its two views.
+static inline DMX_PF_HD bool dmx_pf_filter_w(uint64_t w, uint64_t w2, uint64_t n, uint64_t bit, uint64_t* clp, uint32_t* hdr) {
     if ((w & 7) != 4) return false;   // BFINAL 0, BTYPE 10b (the low bit first)
     const uint32_t hlit = (uint32_t)(w >> 3) & 31, hdist = (uint32_t)(w >> 8) & 31, ncode = ((uint32_t)(w >> 13) & 15) + 4;
     if (hlit > 29 || hdist > 29) return false;
     if (bit + 17 + 3 * ncode > 8 * n) return false;
     const uint8_t order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-    const uint64_t w2 = ncode > 13 ? dmx_pf_peek(z, n, bit + 56) : 0;   // lengths 13..18
     uint64_t cl = 0;
     uint32_t kraft = 0;
     for (uint32_t k = 0; k < ncode; k++) {
-        const uint32_t v = k < 13 ? (uint32_t)(w >> (17 + 3 * k)) & 7 : (uint32_t)(w2 >> (3 * (k - 13))) & 7;
+        const uint32_t v = k < 13 ? (uint32_t)(w >> (17 + 3 * k)) & 7 : (uint32_t)(w2 >> (3 * (k - 13))) & 7;   // lengths 13..18: w2
         cl |= (uint64_t)v << (3 * order[k]);
         if (v) kraft += 128u >> v;
     }
@@ -115,6 +118,12 @@ static inline DMX_PF_HD bool dmx_pf_filter(const uint8_t* z, uint64_t n, uint64_
     *clp = cl;
     *hdr = (uint32_t)w & 0x1FFFF;
     return true;
+}
+static inline DMX_PF_HD bool dmx_pf_filter(const uint8_t* z, uint64_t n, uint64_t bit, uint64_t* clp, uint32_t* hdr) {
+    const uint64_t w = dmx_pf_peek(z, n, bit);
+    if ((w & 7) != 4) return false;
+    const uint64_t w2 = ((uint32_t)(w >> 13) & 15) + 4 > 13 ? dmx_pf_peek(z, n, bit + 56) : 0;
+    return dmx_pf_filter_w(w, w2, n, bit, clp, hdr);
 }
 
 // The full test of a filter survivor, by the rules of the decoder's dynamic-block header (iblock,

@@ -714,6 +714,70 @@ typedef struct { int32_t status; uint32_t format; uint64_t out_len; uint64_t in_
                  uint64_t work_len; } dmx_par_status;                             /* 56 bytes */
 int dmx_inflate_parallel_plan_host(const void* z, uint64_t zbytes, uint32_t fmt, uint32_t chunk_bytes,
                                    dmx_pchunk* chunks, uint32_t cap, dmx_par_status* st);
+/* The same stream decoded in one pass on the device (csrc/dmx_inflate_dev.hip, csrc/dmx_pfind.h,
+ * csrc/dmx_ptail.h; DESIGN.md §3.1 "One foreign stream: the decode"): the plan above built on the
+ * device, then every live chunk decoded by a wave of its own.  Two calls, so that a caller sizes the
+ * output between them (the two-call idiom of dmx_bgzf_read_ranges_async) or captures both with
+ * capacities.  Both follow dmx_inflate_batch_async's rules: no allocation, no host synchronisation;
+ * the number of launches and every grid follow from the host arguments alone (zbytes, chunk_bytes,
+ * max_live, out_cap, verify) and the device's size, a linear chain that can be captured into a
+ * graph; every record and counter is reset by a kernel of the call; workgroups beyond the
+ * device-side counts leave at once.  d_z may have any alignment; the reader loads whole aligned
+ * 4-byte words (up to 3 bytes before d_z, inside the word that holds its first byte, are read and
+ * never looked at) and hands out zeros past d_z + zbytes.
+ * dmx_inflate_parallel_plan_async: four launches (head, find, measure, link) leave in d_plan
+ * (256-byte aligned, plan_bytes >= dmx_inflate_parallel_plan_work(zbytes, chunk_bytes)):
+ *   offset 0     a dmx_par_status: for the same bytes, fmt and chunk_bytes it equals
+ *                dmx_inflate_parallel_plan_host's record field for field, gave_up = 1 with -E_RANGE
+ *                included; behind it in the 256-byte head the chunk_bytes used (uint32 at 56), gzip's
+ *                ISIZE (uint32 at 60), the bit of the first block (uint64 at 64) and zbytes (uint64 at
+ *                72), so the decode needs no repeat of chunk_bytes and fmt
+ *   offset 256   the live chunks, dmx_pchunk[nlive], equal to the host plan's (after a status the
+ *                failing chunk's end_bit and out_len are where its decode stopped: unspecified)
+ *   then         with nc = nchunks and every part rounded up to 256 bytes: room for nc chunks
+ *                (32 nc), the candidates (uint64[nc], the first bit offset of chunk c at which a
+ *                non-final dynamic block can start, or ~0), the measures (32 nc: end_bit, out_len,
+ *                next, flags, status of every candidate's decode for lengths) and 8 KiB of
+ *                first-level tables per workgroup of the measure pass (at most 1 024)
+ * The device measures every candidate in parallel where the host measures only the chunks its walk
+ * reaches; a dead candidate costs time and changes nothing.  chunk_bytes: 0 is the default, else
+ * 1024..2^30.  Returns before any device call: -E_INVAL (d_plan NULL or not 256-byte aligned, d_z
+ * NULL with zbytes > 0, fmt above 3, chunk_bytes out of range, plan_bytes too small), -E_RANGE
+ * (zbytes > 0xFFFFFFF0); else 0 or -E_DEVICE.  dmx_inflate_parallel_plan_work is 0 for arguments
+ * the call refuses, else a multiple of 256, monotone in zbytes.
+ * dmx_inflate_parallel_decode_async: d_plan as the plan call left it for the same d_z and zbytes.
+ * Launches: begin (the plan's record into d_status, the capacity checks, the reset), cells (a wave
+ * per live chunk into 16-bit cells, a match source before the chunk's first byte as a reference
+ * cell), tails (one workgroup walks the chunks in order with the 32 KiB in front of the current one
+ * in LDS and resolves every chunk's last 32 768 cells), pack (cells to bytes; a reference left reads a
+ * cell the tail pass resolved), check (only with verify != 0: Adler-32 sums or CRC-32 remainders per
+ * 64 KiB of output) and status.  *d_status (8-byte aligned):
+ *   the plan's record where the plan has a status (gave_up = 1 with -E_RANGE included): nothing is
+ *     decoded, d_out is untouched;
+ *   -E_SZ when nlive > max_live, out_len > out_cap or work_bytes < dmx_inflate_parallel_work(out_len,
+ *     nlive): the record holds the needed nlive, out_len and work_len, d_out is untouched;
+ *   -E_INVAL for a d_plan that is not a plan of zbytes bytes or needs more than plan_bytes;
+ *   a live chunk's decode error (that of the first such chunk in stream order) where the cell pass
+ *     meets one the measure pass did not: -E_HUFDIS for a distance before the first output byte, -E_SZ
+ *     for a chunk that does not end at its end_bit with its out_len;
+ *   with verify != 0, the trailer: -E_ZADL32 (zlib), -E_CRC, then -E_LEN for ISIZE (gzip); a raw
+ *     stream has none;
+ *   else 0 with format, out_len, in_used, check and the counts as the plan gave them.
+ * After a status other than -E_SZ out_len, in_used, check and work_len are 0 and the bytes of
+ * d_out[0, out_cap) are unspecified; no byte at or beyond out_cap is ever written, and none at or
+ * beyond out_len.  d_work: 256-byte aligned; dmx_inflate_parallel_work(out_cap, max_live) bytes always
+ * suffice (a multiple of 256, monotone in both).  Returns before any device call: -E_INVAL (d_plan,
+ * d_work or d_status NULL, d_z NULL with zbytes > 0, d_out NULL with out_cap > 0; d_plan or d_work
+ * not 256-byte, d_status not 8-byte aligned; plan_bytes below dmx_inflate_parallel_plan_work(1, 0) or work_bytes below 256), -E_RANGE
+ * (zbytes > 0xFFFFFFF0); else 0 or -E_DEVICE. */
+uint64_t dmx_inflate_parallel_plan_work(uint64_t zbytes, uint32_t chunk_bytes);
+int dmx_inflate_parallel_plan_async(const void* d_z, uint64_t zbytes, uint32_t fmt, uint32_t chunk_bytes,
+                                    void* d_plan, uint64_t plan_bytes, void* stream);
+uint64_t dmx_inflate_parallel_work(uint64_t out_cap, uint32_t max_live);
+int dmx_inflate_parallel_decode_async(const void* d_z, uint64_t zbytes, const void* d_plan, uint64_t plan_bytes,
+                                      uint32_t max_live, void* d_out, uint64_t out_cap,
+                                      void* d_work, uint64_t work_bytes, int verify,
+                                      dmx_par_status* d_status, void* stream);
 /* One foreign stream, indexed once and read many times: seek points (csrc/dmx_inflate.c,
  * csrc/dmx_inflate_dev.hip; DESIGN.md §3.1 "Seek points").  The index of zran, indexed_gzip and
  * rapidgzip's --export-index: the stream is decoded once, serially and exactly, on the host, and at
