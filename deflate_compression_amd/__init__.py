@@ -19,6 +19,7 @@ include/dmx.h).  This module is a thin ctypes layer:
     inflate_parallel_plan_host(z)                         ONE zlib / gzip / raw stream cut at true block starts (host)
     inflate_parallel(zt)                                  ... cut on the device and decoded a wave per chunk, in one pass
     zindex_build(z) -> ZIndex                             ONE such stream indexed once on the host: seek points with windows
+    inflate_parallel_indexed(zt) -> (out, ZIndex)         ... decoded in one pass on the device, which leaves the same index there
     inflate_indexed(zt, ix) / zindex_pread(zt, ix, off, n)  ... then decoded a wave per point, or only the points a range touches
     compress_batch(bufs)                                  many independent buffers into as many streams, in one chain of launches
     Encoder                                               device-resident encodes
@@ -47,6 +48,7 @@ __all__ = [
     "inflate_parallel", "inflate_parallel_plan_async", "inflate_parallel_decode_async",
     "ZIndex", "ZIndexStatus", "zindex_build", "inflate_points_async", "inflate_indexed", "zindex_read_ranges", "zindex_pread",
     "DMX_ZINDEX_WINDOW", "DMX_ZINDEX_DEF_SPAN", "DMX_ZINDEX_MAX_SPAN",
+    "zindex_from_parallel_async", "inflate_parallel_indexed",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -269,6 +271,11 @@ def lib() -> ctypes.CDLL:
         "dmx_zindex_build_host": ([vp, u64, u32, u32, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
                                    ctypes.POINTER(ZIndexStatus)], ctypes.c_int),
         "dmx_inflate_points_work": ([u32], u64),
+        "dmx_zindex_points_bound": ([u64, u32, u32], u32),
+        "dmx_zindex_device_work": ([u64, u32], u64),
+        "dmx_zindex_from_parallel_async": ([vp, u64, vp, vp, u64, u32, u32, vp, vp, vp, u32, vp, u64, vp, vp], ctypes.c_int),
+        "dmx_zindex_from_chunks_host": ([vp, u32, vp, u64, u32, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
+                                         u32p], ctypes.c_int),
         "dmx_inflate_points_async": ([vp, u64, vp, vp, vp, u32, vp, vp, u32, vp, u64, vp, vp, u64, vp, vp], ctypes.c_int),
         "dmx_encode_batch_blocks": ([u64, u32, i32], u32),
         "dmx_encode_batch_bound": ([u64, u32, i32, u32], u64),
@@ -1121,6 +1128,105 @@ def zindex_build(z, fmt: str = "auto", span: int | None = None) -> ZIndex:
         for p in (pts, adl, win):
             _libc.free(p)
     return ZIndex(points, adlers, windows, rec.format, rec.out_len, rec.in_used, rec.check, rec.span)
+
+
+def zindex_from_parallel_async(plan, dec_status, out, out_cap: int, max_live: int, span: int, points, adlers, windows,
+                               max_points: int, work, status, stream=None) -> int:
+    """dmx_zindex_from_parallel_async on caller-owned CUDA tensors, enqueued on `stream` (the current
+    one by default) behind inflate_parallel_decode_async with no synchronisation, so plan, decode and
+    index can be captured into one graph: plan, out and dec_status (the decode's 56-byte record) as
+    those calls left them, out_cap and max_live the decode's capacities, span 0 for the default;
+    points 32 x max_points bytes, adlers 4 x max_points, windows 32768 x max_points; work a uint8 tensor
+    of lib().dmx_zindex_device_work(out_cap, max_points) bytes (256-byte aligned); status a 40-byte
+    tensor (ZIndexStatus).  Returns the call's own return code; the outcome is in the record."""
+    import torch
+    dev = work.device
+    with torch.cuda.device(dev):
+        s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        return lib().dmx_zindex_from_parallel_async(_ptr(plan), plan.numel() if plan is not None else 0, _ptr(dec_status),
+                                                    _ptr(out), out_cap, max_live, span, _ptr(points), _ptr(adlers),
+                                                    _ptr(windows), max_points, ctypes.c_void_p(work.data_ptr()), work.numel(),
+                                                    _ptr(status), ctypes.c_void_p(s))
+
+
+def inflate_parallel_indexed(z, fmt: str = "auto", chunk_bytes: int | None = None, span: int | None = None,
+                             verify: bool = True, info: dict | None = None):
+    """inflate_parallel that also leaves the stream's seek-point index: returns (out, ZIndex).  The
+    plan, its one synchronisation, the allocations and the decode are inflate_parallel's; the index
+    call (dmx_zindex_from_parallel_async) follows on the same stream, sized by
+    dmx_zindex_points_bound, its record is the one copy that is waited for (after -E_SZ the call runs
+    once more with the npoints it names), and the index is copied to the host for the ZIndex, whose
+    per-device cache is seeded with the device tensors: inflate_indexed, zindex_read_ranges and
+    zindex_pread then upload nothing.  A point begins at the first chunk boundary `span` bytes of
+    output behind the point before (default 256 KiB).  Where inflate_parallel takes the serial route
+    (the plan gave the stream up, or found one chunk), out comes from that route and the index from
+    zindex_build on the stream's bytes copied to the host.  info (a dict) receives the plan's and the
+    decode's fields, route as inflate_parallel, index_route "device" or "host", and npoints."""
+    if fmt not in _BATCH_FMT:
+        raise ValueError("fmt is one of " + ", ".join(_BATCH_FMT))
+    sp = int(span or 0)
+    if sp < 0 or sp > DMX_ZINDEX_MAX_SPAN:
+        raise ValueError("span is 1 .. 2^30 (None or 0: the default)")
+    import numpy as np
+    import torch
+    if isinstance(z, torch.Tensor):
+        if z.numel() and (z.dtype != torch.uint8 or not z.is_cuda or not z.is_contiguous()):
+            raise ValueError("inflate_parallel_indexed takes a contiguous uint8 CUDA tensor")
+        zt = z
+    else:
+        b = bytes(z)
+        zt = torch.frombuffer(bytearray(b or b"\0"), dtype=torch.uint8).cuda()[:len(b)]
+    L = lib()
+    dev = zt.device
+    cb = int(chunk_bytes or 0)
+    pb = int(L.dmx_inflate_parallel_plan_work(zt.numel(), cb))
+    if not pb:
+        raise ValueError("chunk_bytes is 1024 .. 2^30 (None or 0: the default), the stream at most 0xFFFFFFF0 bytes")
+    plan = torch.empty(pb, dtype=torch.uint8, device=dev)
+    _check(inflate_parallel_plan_async(zt, _BATCH_FMT[fmt], cb, plan), "dmx_inflate_parallel_plan_async")
+    rec = ParStatus.from_buffer_copy(plan[:56].cpu().numpy().tobytes())   # the one synchronisation before the decode
+    if info is not None:
+        info.update(_par_info(rec))
+        info["route"], info["index_route"] = "parallel", "device"
+    if rec.gave_up or (rec.status == 0 and rec.nlive == 1):
+        if info is not None:
+            info["route"], info["index_route"] = "serial", "host"
+        out, _, res = inflate_batch(zt, [(0, zt.numel())], fmt=fmt)
+        ix = zindex_build(zt.cpu().numpy(), fmt=fmt, span=sp)
+        if info is not None:
+            info["npoints"] = ix.npoints
+        return out[:int(res["out_len"][0])], ix
+    if rec.status:
+        raise DeflateError(rec.status, "inflate_parallel_indexed")
+    out = torch.empty(max(rec.out_len, 1), dtype=torch.uint8, device=dev)
+    work = torch.empty(int(rec.work_len), dtype=torch.uint8, device=dev)
+    st = torch.empty(7, dtype=torch.int64, device=dev)
+    _check(inflate_parallel_decode_async(zt, plan, rec.nlive, out, rec.out_len, work, verify, st),
+           "dmx_inflate_parallel_decode_async")
+    cap = int(L.dmx_zindex_points_bound(rec.out_len, rec.nlive, sp))
+    zst = torch.empty(5, dtype=torch.int64, device=dev)
+    for attempt in (0, 1):
+        pts = torch.empty((cap, 4), dtype=torch.int64, device=dev)
+        adl = torch.empty(cap, dtype=torch.int32, device=dev)
+        win = torch.empty((cap, DMX_ZINDEX_WINDOW), dtype=torch.uint8, device=dev)
+        zwork = torch.empty(int(L.dmx_zindex_device_work(rec.out_len, cap)), dtype=torch.uint8, device=dev)
+        _check(zindex_from_parallel_async(plan, st, out, rec.out_len, rec.nlive, sp, pts, adl, win, cap, zwork, zst),
+               "dmx_zindex_from_parallel_async")
+        zrec = ZIndexStatus.from_buffer_copy(zst.cpu().numpy().tobytes())
+        if attempt == 0 and zrec.status == -E["E_SZ"] and zrec.npoints > cap:
+            cap = int(zrec.npoints)
+            continue
+        break
+    if info is not None:
+        info.update({f: int(getattr(zrec, f)) for f, _ in ZIndexStatus._fields_ if f != "reserved"})
+    if zrec.status:
+        raise DeflateError(zrec.status, "inflate_parallel_indexed")
+    n = int(zrec.npoints)
+    pts, adl, win = pts[:n], adl[:n], win[:n]
+    ix = ZIndex(pts.cpu().numpy().view(np.uint8).reshape(-1).view(PCHUNK_DTYPE), adl.cpu().numpy().view(np.uint32),
+                win.cpu().numpy(), zrec.format, zrec.out_len, zrec.in_used, zrec.check, zrec.span)
+    ix._dev[torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())] = (pts, adl, win)
+    return out[:zrec.out_len], ix
 
 
 def inflate_points_async(zt, points, adlers, windows, npoints: int, sel, dst_off, nsel: int, out, out_bytes: int, results,

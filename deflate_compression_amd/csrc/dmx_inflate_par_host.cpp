@@ -11,6 +11,7 @@
 #include "../../include/dmx.h"
 #include "dmx_gz_head.h"
 #include "dmx_pfind.h"
+#include "dmx_zsel.h"
 
 namespace {
 
@@ -289,4 +290,71 @@ extern "C" int dmx_inflate_parallel_plan_host(const void* zv, uint64_t zbytes, u
     free(cand);
     free(meas);
     return st->nlive > cap ? -(int)E_SZ : 0;
+}
+
+// ---- seek points from a plan's live chunks (include/dmx.h: dmx_zindex_from_chunks_host) ----------
+extern "C" uint32_t dmx_zindex_points_bound(uint64_t out_cap, uint32_t max_live, uint32_t span) {
+    return dmx_zs_bound(out_cap, max_live, span);
+}
+
+extern "C" uint64_t dmx_zindex_device_work(uint64_t out_cap, uint32_t max_points) { return dmx_zs_work(out_cap, max_points); }
+
+static uint32_t zs_adler32(const uint8_t* d, uint64_t n) {
+    uint32_t a = 1, b = 0;
+    while (n) {
+        uint64_t k = n < 5552 ? n : 5552;
+        n -= k;
+        while (k--) { a += *d++; b += a; }
+        a %= 65521u;
+        b %= 65521u;
+    }
+    return (b << 16) | a;
+}
+
+// The host twin of dmx_zindex_from_parallel_async: dmx_zs_select over the chunks, then every point's
+// window and Adler-32 from the decoded bytes.  The chunks must tile out[0, out_len) in order.
+extern "C" int dmx_zindex_from_chunks_host(const dmx_pchunk* chunks, uint32_t nlive, const void* outv, uint64_t out_len,
+                                           uint32_t span, dmx_zpoint** points, uint32_t** adlers, uint8_t** windows,
+                                           uint32_t* npoints) {
+    if (!chunks || !nlive || (!outv && out_len) || !points || !adlers || !windows || !npoints) return -(int)E_INVAL;
+    if (span > DMX_ZINDEX_MAX_SPAN) return -(int)E_RANGE;
+    *points = NULL;
+    *adlers = NULL;
+    *windows = NULL;
+    *npoints = 0;
+    uint64_t off = 0;
+    for (uint32_t c = 0; c < nlive; c++) {
+        if (chunks[c].out_off != off || chunks[c].out_len > out_len - off) return -(int)E_INVAL;
+        off += chunks[c].out_len;
+    }
+    if (off != out_len) return -(int)E_INVAL;
+    const uint32_t sp = dmx_zs_span(span);
+    const uint32_t n = dmx_zs_select(chunks, nlive, sp, NULL, NULL, 0);
+    dmx_zpoint* p = (dmx_zpoint*)malloc(n * sizeof(dmx_zpoint));
+    uint32_t* a = (uint32_t*)malloc(n * sizeof(uint32_t));
+    uint32_t* base = (uint32_t*)malloc((n + 1ull) * sizeof(uint32_t));
+    uint8_t* w = (uint8_t*)malloc(n * (uint64_t)DMX_ZINDEX_WINDOW);
+    if (!p || !a || !base || !w) {
+        free(p);
+        free(a);
+        free(base);
+        free(w);
+        return -(int)E_MALLOC;
+    }
+    dmx_zs_select(chunks, nlive, sp, p, base, n);
+    free(base);
+    const uint8_t* out = (const uint8_t*)outv;
+    for (uint32_t k = 0; k < n; k++) {
+        const uint64_t o = p[k].out_off;
+        const size_t wlen = o < DMX_ZINDEX_WINDOW ? (size_t)o : DMX_ZINDEX_WINDOW;
+        uint8_t* slot = w + k * (uint64_t)DMX_ZINDEX_WINDOW;
+        memset(slot, 0, DMX_ZINDEX_WINDOW - wlen);
+        if (wlen) memcpy(slot + (DMX_ZINDEX_WINDOW - wlen), out + (o - wlen), wlen);
+        a[k] = zs_adler32(out ? out + o : NULL, p[k].out_len);
+    }
+    *points = p;
+    *adlers = a;
+    *windows = w;
+    *npoints = n;
+    return 0;
 }

@@ -858,6 +858,64 @@ int dmx_inflate_points_async(const void* d_z, uint64_t zbytes, const dmx_zpoint*
                              const uint64_t* d_dst_off,   /* NULL: the points' own out_off */
                              uint32_t nsel, void* d_out, uint64_t out_bytes, dmx_bresult* d_results,
                              void* d_work, uint64_t work_bytes, dmx_batch_status* d_status, void* stream);
+/* Seek points from the one-pass decode (csrc/dmx_zindex_dev.hip, csrc/dmx_zsel.h; DESIGN.md §3.1 "Seek
+ * points from the one-pass decode").  When dmx_inflate_parallel_decode_async ends, everything an index
+ * holds is on the device: the live chunks in the plan buffer are true block boundaries with exact bit,
+ * end_bit, out_off and out_len, and d_out supplies every window and every point's Adler-32.  So the
+ * first read of a foreign stream costs about one one-pass decode and leaves the index of the calls
+ * above in device memory: no host decode, and the stream never leaves the device.
+ * The selection is dmx_zindex_build_host's rule restricted to chunk boundaries (dmx_zsel.h, one text
+ * for host and device): point 0 is live chunk 0 (out_off 0, no window); a further point begins at the
+ * first live chunk at which the output since the point before began is >= span (0: DMX_ZINDEX_DEF_SPAN,
+ * else 1 .. DMX_ZINDEX_MAX_SPAN; 1: every live chunk that follows output).  A point has the bit and
+ * out_off of its first chunk, the next point's bit as end_bit (the last: the last live chunk's
+ * end_bit) and the sum of its chunks' out_len; a last chunk of no output behind such a boundary is a
+ * last point of length 0, as on the host.  Every point but the last holds at least min(span, out_len)
+ * bytes, so npoints <= min(out_len / span + 1, nlive): dmx_zindex_points_bound(out_cap, max_live, span)
+ * is that bound for capacities, at least 1.  Every point is a run of whole blocks.
+ * dmx_zindex_from_parallel_async runs behind dmx_inflate_parallel_decode_async on the same stream:
+ * d_plan and d_out as those two calls left them, *d_dec_status the decode call's record (8-byte
+ * aligned, device memory), out_cap and max_live the decode's capacities.  It follows their rules: no
+ * allocation, no host synchronisation; four launches (select, windows, fold, finish) whose grids
+ * follow from out_cap, max_live, max_points and span alone and the device's size, a linear chain that
+ * can be captured into one graph with plan and decode; every record and counter is reset by a kernel
+ * of the call; workgroups beyond the device-side counts leave at once.  d_plan and d_out are read,
+ * never written.  *d_status (dmx_zindex_status, 40 bytes, 8-byte aligned):
+ *   a decode record with a status: that status, -E_SZ included, with format and span; everything else
+ *     is 0 and nothing of the three arrays is written;
+ *   -E_INVAL for a record that does not fit d_plan, out_cap and max_live (nlive 0 or above max_live,
+ *     out_len above out_cap, chunks beyond plan_bytes or that do not end at out_len);
+ *   -E_SZ when npoints > max_points or work_bytes < dmx_zindex_device_work(out_len, npoints): the
+ *     record holds the needed npoints, and format, out_len and span; nothing of the three arrays is
+ *     written (the two-call idiom);
+ *   else 0 with format, out_len, in_used and check from the decode's record, npoints, and span the
+ *     value used.  d_points[0, npoints) follow the rule above; d_adlers[k] is the Adler-32 of
+ *     d_out[out_off, out_off + out_len) -- always Adler-32, whatever the stream's own check is: it is
+ *     what dmx_inflate_points_async compares; slot k of d_windows (DMX_ZINDEX_WINDOW bytes each) holds
+ *     the wlen = min(out_off, 32768) bytes in front of out_off right-aligned, zeros before them.  No
+ *     byte at or beyond d_points[npoints], d_adlers[npoints] or slot npoints is written.
+ * The source of a window lies at any byte alignment: whole aligned 16-byte groups inside
+ * d_out[0, out_len) are loaded, single bytes at its ends, nothing outside it.  d_work: 256-byte
+ * aligned; dmx_zindex_device_work(out_cap, max_points) bytes always suffice (a multiple of 256,
+ * monotone in both).  Returns before any device call: -E_INVAL (a NULL pointer; d_plan or d_work not
+ * 256-byte, d_points, d_dec_status or d_status not 8-byte, d_adlers not 4-byte aligned; plan_bytes
+ * below dmx_inflate_parallel_plan_work(1, 0) or work_bytes below dmx_zindex_device_work(0, 1)),
+ * -E_RANGE (span above 2^30); else 0 or -E_DEVICE.
+ * dmx_zindex_from_chunks_host is the host twin, no GPU: the same three arrays, malloc'd (the caller
+ * frees each with free()), from the plan's live chunks (dmx_inflate_parallel_plan_host) and the
+ * decoded bytes out[0, out_len), which the chunks must tile in order (else -E_INVAL, as for a NULL
+ * pointer or nlive 0).  For the same chunks, bytes and span the device's arrays equal them byte for
+ * byte.  Returns 0, -E_INVAL, -E_RANGE (span) or -E_MALLOC. */
+uint32_t dmx_zindex_points_bound(uint64_t out_cap, uint32_t max_live, uint32_t span);
+uint64_t dmx_zindex_device_work(uint64_t out_cap, uint32_t max_points);
+int dmx_zindex_from_parallel_async(const void* d_plan, uint64_t plan_bytes,
+                                   const dmx_par_status* d_dec_status,   /* the decode call's record */
+                                   const void* d_out, uint64_t out_cap, uint32_t max_live, uint32_t span,
+                                   dmx_zpoint* d_points, uint32_t* d_adlers, void* d_windows, uint32_t max_points,
+                                   void* d_work, uint64_t work_bytes, dmx_zindex_status* d_status, void* stream);
+int dmx_zindex_from_chunks_host(const dmx_pchunk* chunks, uint32_t nlive, const void* out, uint64_t out_len,
+                                uint32_t span, dmx_zpoint** points, uint32_t** adlers, uint8_t** windows,
+                                uint32_t* npoints);
 /* Batches of independent buffers into independent streams (csrc/dmx_encode_batch.hip):
  * the encode's counterpart of dmx_inflate_batch_async.  nstreams buffers become nstreams complete
  * zlib streams, gzip members or raw DEFLATE streams, every one decodable on its own, in one chain of
