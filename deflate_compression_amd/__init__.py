@@ -18,6 +18,11 @@ include/dmx.h).  This module is a thin ctypes layer:
                                                           (zdict=: preset dictionaries, zlib's FDICT / inflateSetDictionary)
     inflate_parallel_plan_host(z)                         ONE zlib / gzip / raw stream cut at true block starts (host)
     inflate_parallel(zt)                                  ... cut on the device and decoded a wave per chunk, in one pass
+    inflate_parallel_multi_plan_host(z)                   ONE .gz file of many members (cat a.gz b.gz, WARC) cut the same way (host)
+    inflate_parallel_multi(zt) -> (out, members)          ... decoded in one pass on the device, every member's CRC-32 checked there
+    inflate_parallel_multi_plan_async / inflate_parallel_multi_decode_async
+                                                          ... the two device calls on caller-owned tensors, for a graph
+                                                          (records: ParMultiStatus, PMember / PMEMBER_DTYPE)
     zindex_build(z) -> ZIndex                             ONE such stream indexed once on the host: seek points with windows
     inflate_parallel_indexed(zt) -> (out, ZIndex)         ... decoded in one pass on the device, which leaves the same index there
     inflate_indexed(zt, ix) / zindex_pread(zt, ix, off, n)  ... then decoded a wave per point, or only the points a range touches
@@ -46,6 +51,8 @@ __all__ = [
     "compress_batch_dict_async",
     "inflate_parallel_plan_host", "PChunk", "ParStatus", "PCHUNK_DTYPE",
     "inflate_parallel", "inflate_parallel_plan_async", "inflate_parallel_decode_async",
+    "PMember", "PMEMBER_DTYPE", "ParMultiStatus", "inflate_parallel_multi_plan_host", "inflate_parallel_multi_plan_async",
+    "inflate_parallel_multi_decode_async", "inflate_parallel_multi",
     "ZIndex", "ZIndexStatus", "zindex_build", "inflate_points_async", "inflate_indexed", "zindex_read_ranges", "zindex_pread",
     "DMX_ZINDEX_WINDOW", "DMX_ZINDEX_DEF_SPAN", "DMX_ZINDEX_MAX_SPAN",
     "zindex_from_parallel_async", "inflate_parallel_indexed",
@@ -165,6 +172,17 @@ class ParStatus(ctypes.Structure):
                 ("gave_up", ctypes.c_uint32), ("work_len", ctypes.c_uint64)]
 
 
+class PMember(ctypes.Structure):
+    """dmx_pmember: one gzip member of a file of many -- where it lies in the file and in the output, its trailer"""
+    _fields_ = [("in_off", ctypes.c_uint64), ("out_off", ctypes.c_uint64), ("out_len", ctypes.c_uint64),
+                ("crc", ctypes.c_uint32), ("isize", ctypes.c_uint32)]
+
+
+class ParMultiStatus(ctypes.Structure):
+    """dmx_par_multi_status: the 64-byte record of dmx_inflate_parallel_multi_plan_host"""
+    _fields_ = [("st", ParStatus), ("nmembers", ctypes.c_uint32), ("bad_member", ctypes.c_uint32)]
+
+
 class ZIndexStatus(ctypes.Structure):
     """dmx_zindex_status: the 40-byte record of dmx_zindex_build_host"""
     _fields_ = [("status", ctypes.c_int32), ("format", ctypes.c_uint32), ("out_len", ctypes.c_uint64),
@@ -174,6 +192,9 @@ class ZIndexStatus(ctypes.Structure):
 
 # numpy's view of dmx_pchunk records
 PCHUNK_DTYPE = [("bit", "<u8"), ("end_bit", "<u8"), ("out_off", "<u8"), ("out_len", "<u8")]
+
+# numpy's view of dmx_pmember records
+PMEMBER_DTYPE = [("in_off", "<u8"), ("out_off", "<u8"), ("out_len", "<u8"), ("crc", "<u4"), ("isize", "<u4")]
 
 # numpy's view of dmx_bresult records
 BRESULT_DTYPE = [("status", "<i4"), ("format", "<u4"), ("out_len", "<u8"), ("in_used", "<u8"), ("check", "<u4"),
@@ -268,6 +289,13 @@ def lib() -> ctypes.CDLL:
         "dmx_inflate_parallel_plan_async": ([vp, u64, u32, u32, vp, u64, vp], ctypes.c_int),
         "dmx_inflate_parallel_work": ([u64, u32], u64),
         "dmx_inflate_parallel_decode_async": ([vp, u64, vp, u64, u32, vp, u64, vp, u64, ctypes.c_int, vp, vp], ctypes.c_int),
+        "dmx_inflate_parallel_multi_plan_host": ([vp, u64, u32, u32, vp, u32, vp, u32, ctypes.POINTER(ParMultiStatus)],
+                                                 ctypes.c_int),
+        "dmx_inflate_parallel_multi_plan_work": ([u64, u32], u64),
+        "dmx_inflate_parallel_multi_plan_async": ([vp, u64, u32, u32, vp, u64, vp], ctypes.c_int),
+        "dmx_inflate_parallel_multi_work": ([u64, u32, u32], u64),
+        "dmx_inflate_parallel_multi_decode_async": ([vp, u64, vp, u64, u32, u32, vp, u64, vp, vp, u64, ctypes.c_int, vp, vp],
+                                                    ctypes.c_int),
         "dmx_zindex_build_host": ([vp, u64, u32, u32, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
                                    ctypes.POINTER(ZIndexStatus)], ctypes.c_int),
         "dmx_inflate_points_work": ([u32], u64),
@@ -1037,6 +1065,149 @@ def inflate_parallel(z, fmt: str = "auto", chunk_bytes: int | None = None, verif
     if rec.status:
         raise DeflateError(rec.status, "inflate_parallel")
     return out[:rec.out_len]
+
+
+def _par_multi_info(rec: ParMultiStatus) -> dict:
+    d = _par_info(rec.st)
+    d["nmembers"], d["bad_member"] = int(rec.nmembers), int(rec.bad_member)
+    return d
+
+
+def inflate_parallel_multi_plan_host(z, chunk_bytes: int | None = None):
+    """One .gz file of many members (RFC 1952 2.2: `cat a.gz b.gz`, rotated logs, pgzip, WARC) cut into
+    chunks that begin at true block boundaries or member starts, on the host
+    (dmx_inflate_parallel_multi_plan_host): returns (chunks, members, info) -- the live chunks as
+    PCHUNK_DTYPE records, the members as PMEMBER_DTYPE records (in_off, out_off, out_len and the stored
+    crc and isize), and the record's fields as a dict (status included, nmembers, bad_member)."""
+    import numpy as np
+    zp, zn, zk = _buf(z)
+    rec = ParMultiStatus()
+    cb = int(chunk_bytes or 0)
+    r = lib().dmx_inflate_parallel_multi_plan_host(zp, zn, DMX_BATCH_GZIP, cb, None, 0, None, 0, ctypes.byref(rec))
+    ok = r in (0, -E["E_SZ"])
+    chunks = np.zeros(rec.st.nlive if ok else 0, dtype=PCHUNK_DTYPE)
+    members = np.zeros(rec.nmembers if ok else 0, dtype=PMEMBER_DTYPE)
+    if r == -E["E_SZ"]:
+        r = lib().dmx_inflate_parallel_multi_plan_host(zp, zn, DMX_BATCH_GZIP, cb, ctypes.c_void_p(chunks.ctypes.data),
+                                                       chunks.shape[0], ctypes.c_void_p(members.ctypes.data),
+                                                       members.shape[0], ctypes.byref(rec))
+    del zk
+    _check(r, "dmx_inflate_parallel_multi_plan_host")
+    return chunks, members, _par_multi_info(rec)
+
+
+def inflate_parallel_multi_plan_async(zt, fmt: int, chunk_bytes: int, plan, stream=None) -> int:
+    """dmx_inflate_parallel_multi_plan_async on caller-owned CUDA tensors, as inflate_parallel_plan_async:
+    fmt DMX_BATCH_AUTO or DMX_BATCH_GZIP, plan a uint8 tensor of
+    lib().dmx_inflate_parallel_multi_plan_work(zt.numel(), chunk_bytes) bytes (256-byte aligned) whose
+    first 64 bytes receive the ParMultiStatus record.  Returns the call's own return code."""
+    import torch
+    dev = plan.device
+    with torch.cuda.device(dev):
+        s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        return lib().dmx_inflate_parallel_multi_plan_async(_ptr(zt), zt.numel() if zt is not None else 0, fmt, chunk_bytes,
+                                                           ctypes.c_void_p(plan.data_ptr()), plan.numel(), ctypes.c_void_p(s))
+
+
+def inflate_parallel_multi_decode_async(zt, plan, max_live: int, max_members: int, out, out_cap: int, members, work,
+                                        verify: bool, status, stream=None) -> int:
+    """dmx_inflate_parallel_multi_decode_async on caller-owned CUDA tensors (no synchronisation: plan and
+    decode can be captured into one graph): plan as the plan call left it for zt; max_live, max_members
+    and out_cap the capacities; members a tensor of 32 x max_members bytes (8-byte aligned) for the
+    PMember records; work a uint8 tensor of at least lib().dmx_inflate_parallel_multi_work(out_len, nlive,
+    nmembers) bytes (256-byte aligned); status a 64-byte tensor (ParMultiStatus).  Returns the call's own
+    return code; the outcome is in the record."""
+    import torch
+    dev = work.device
+    with torch.cuda.device(dev):
+        s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        return lib().dmx_inflate_parallel_multi_decode_async(_ptr(zt), zt.numel() if zt is not None else 0,
+                                                             ctypes.c_void_p(plan.data_ptr()), plan.numel(), max_live,
+                                                             max_members, _ptr(out), out_cap, _ptr(members),
+                                                             ctypes.c_void_p(work.data_ptr()), work.numel(),
+                                                             1 if verify else 0, ctypes.c_void_p(status.data_ptr()),
+                                                             ctypes.c_void_p(s))
+
+
+def _multi_serial(zt, info):
+    """the serial route of inflate_parallel_multi: member by member through inflate_batch, each stream
+    from the member before's in_used on; the same member table, built on the host"""
+    import numpy as np
+    import torch
+    n = zt.numel()
+    pos, total, outs, rows = 0, 0, [], []
+    while True:
+        o, _, res = inflate_batch(zt, [(pos, n - pos)], fmt="gzip", strict=False)
+        st = int(res["status"][0])
+        if st:
+            raise DeflateError(st, f"inflate_parallel_multi: member {len(rows)}")
+        olen, used = int(res["out_len"][0]), int(res["in_used"][0])
+        isize = int.from_bytes(zt[pos + used - 4:pos + used].cpu().numpy().tobytes(), "little")
+        rows.append((pos, total, olen, int(res["check"][0]), isize))
+        outs.append(o[:olen])
+        total += olen
+        pos += used
+        if pos + 2 > n or zt[pos:pos + 2].cpu().numpy().tobytes() != b"\x1f\x8b":
+            break
+    if info is not None:
+        info.update(status=0, out_len=total, in_used=pos, check=rows[-1][3], nmembers=len(rows), bad_member=0xFFFFFFFF)
+    out = torch.cat(outs) if total else torch.empty(0, dtype=torch.uint8, device=zt.device)
+    return out, np.array(rows, dtype=PMEMBER_DTYPE)
+
+
+def inflate_parallel_multi(z, chunk_bytes: int | None = None, verify: bool = True, info: dict | None = None):
+    """One .gz file of many members decoded in one pass on the GPU: z a contiguous uint8 CUDA tensor
+    (or bytes, copied to the device here).  As inflate_parallel: the plan
+    (dmx_inflate_parallel_multi_plan_async), one synchronisation for its 64-byte record, the
+    allocations, the decode (dmx_inflate_parallel_multi_decode_async) -- but the walk goes on behind
+    every trailer while 1F 8B follows; anything else there is trailing data and ignored (info["in_used"]
+    says where it begins).  verify: every member's CRC-32 and ISIZE are checked on the device; a failure
+    raises DeflateError whose message names the member.  Where the plan gave the file up or found one
+    live chunk, the file goes member by member through inflate_batch (info["route"] == "serial": slow
+    and correct, always verified).  info receives the record's fields and route.  Returns (out,
+    members): the members' data back to back as a uint8 CUDA tensor and a numpy array of
+    PMEMBER_DTYPE records."""
+    import numpy as np
+    import torch
+    if isinstance(z, torch.Tensor):
+        if z.numel() and (z.dtype != torch.uint8 or not z.is_cuda or not z.is_contiguous()):
+            raise ValueError("inflate_parallel_multi takes a contiguous uint8 CUDA tensor")
+        zt = z
+    else:
+        b = bytes(z)
+        zt = torch.frombuffer(bytearray(b or b"\0"), dtype=torch.uint8).cuda()[:len(b)]
+    L = lib()
+    dev = zt.device
+    cb = int(chunk_bytes or 0)
+    pb = int(L.dmx_inflate_parallel_multi_plan_work(zt.numel(), cb))
+    if not pb:
+        raise ValueError("chunk_bytes is 1024 .. 2^30 (None or 0: the default), the file at most 0xFFFFFFF0 bytes")
+    plan = torch.empty(pb, dtype=torch.uint8, device=dev)
+    _check(inflate_parallel_multi_plan_async(zt, DMX_BATCH_GZIP, cb, plan), "dmx_inflate_parallel_multi_plan_async")
+    rec = ParMultiStatus.from_buffer_copy(plan[:64].cpu().numpy().tobytes())   # the one synchronisation before the decode
+    if info is not None:
+        info.update(_par_multi_info(rec))
+        info["route"] = "parallel"
+    if rec.st.gave_up or (rec.st.status == 0 and rec.st.nlive == 1):
+        if info is not None:
+            info["route"] = "serial"
+        return _multi_serial(zt, info)
+    if rec.st.status:
+        raise DeflateError(rec.st.status, "inflate_parallel_multi")
+    out = torch.empty(max(rec.st.out_len, 1), dtype=torch.uint8, device=dev)
+    work = torch.empty(int(rec.st.work_len), dtype=torch.uint8, device=dev)
+    mem = torch.empty(4 * rec.nmembers, dtype=torch.int64, device=dev)
+    st = torch.empty(8, dtype=torch.int64, device=dev)
+    _check(inflate_parallel_multi_decode_async(zt, plan, rec.st.nlive, rec.nmembers, out, rec.st.out_len, mem, work, verify, st),
+           "dmx_inflate_parallel_multi_decode_async")
+    rec = ParMultiStatus.from_buffer_copy(st.cpu().numpy().tobytes())
+    if info is not None:
+        info.update(_par_multi_info(rec))
+    if rec.st.status:
+        where = f": member {rec.bad_member}" if rec.bad_member != 0xFFFFFFFF else ""
+        raise DeflateError(rec.st.status, "inflate_parallel_multi" + where)
+    members = mem.cpu().numpy().view(np.uint8).reshape(-1).view(PMEMBER_DTYPE).copy()
+    return out[:rec.st.out_len], members
 
 
 class ZIndex:

@@ -1628,12 +1628,33 @@ struct PPlanHead {   // the first 256 bytes of d_plan
     unsigned long long next;   // 80: the measure pass's claim counter
 };
 static_assert(sizeof(dmx_par_status) == 56 && sizeof(PPlanHead) <= 256 && sizeof(dmx_pf_meas) == 32, "d_plan's layout");
+struct PMPlanHead {   // a file of members: the 64-byte record (dmx_par_multi_status) in front
+    dmx_par_status st;               // 0
+    uint32_t nmembers, bad_member;   // 56, 60
+    uint32_t chunk_bytes;            // 64
+    uint32_t isize;                  // 68: the last member's ISIZE
+    uint64_t body_bit;               // 72: 0, the first header
+    uint64_t zbytes;                 // 80
+    unsigned long long next;         // 88
+};
+static_assert(sizeof(dmx_par_multi_status) == 64 && offsetof(PMPlanHead, chunk_bytes) == 64 && sizeof(PMPlanHead) <= 256 &&
+                  sizeof(dmx_pf_mside) == 16 && sizeof(dmx_pmember) == 32,
+              "d_plan's layout, many members");
+template <bool MULTI>
+using PHead = typename std::conditional<MULTI, PMPlanHead, PPlanHead>::type;
+// the sides in a plan of many members, behind the walks' member offsets (begin has checked plan_bytes)
+__device__ __forceinline__ const dmx_pf_mside* pm_sides(const uint8_t* plan) {
+    const uint32_t nc = reinterpret_cast<const PMPlanHead*>(plan)->st.nchunks;
+    return reinterpret_cast<const dmx_pf_mside*>(plan + 256 + 2 * dmx_pf_a256(32ull * nc) + 2 * dmx_pf_a256(8ull * nc));
+}
 
 struct PDecCtl {   // the first 256 bytes of d_work
     unsigned long long next;   // the cell pass's claim counter
     unsigned long long err;    // chunk << 32 | status, an integer minimum: the first chunk's error
     uint64_t out_len;
     uint32_t go, nlive, format, check, isize;
+    uint32_t nmembers;         // a file of members (dmx_inflate_parallel_multi_decode_async) from here on
+    unsigned long long bad;    // member << 32 | status: the first member whose check fails
 };
 #define PDEC_NOERR (~0ull)
 __device__ __forceinline__ void pdec_fail(PDecCtl* ctl, uint32_t chunk, int err) {
@@ -1677,8 +1698,9 @@ __device__ __forceinline__ uint32_t par_word(const uint8_t* zb, uint32_t mis, ui
     return v;
 }
 
+template <bool MULTI>
 __global__ __launch_bounds__(64) void dmx_par_find_kernel(const uint8_t* __restrict__ z, uint64_t zbytes,
-                                                          PPlanHead* __restrict__ h, uint64_t* __restrict__ cand) {
+                                                          PHead<MULTI>* __restrict__ h, uint64_t* __restrict__ cand) {
     const uint32_t c = blockIdx.x, lane = threadIdx.x;
     if (c == 0 || h->st.status) return;   // chunk 0 begins at the framing's bit
     uint64_t lo, hi;
@@ -1708,6 +1730,10 @@ __global__ __launch_bounds__(64) void dmx_par_find_kernel(const uint8_t* __restr
         const bool pass = bit < hi && dmx_pf_filter_w(w, w2, zbytes, bit, &cl, &hdr);
         bool ok = false;
         if (__ballot(pass)) ok = pass && dmx_pf_header(z, zbytes, bit, cl, hdr);
+        if constexpr (MULTI) {   // a member start, in the lanes whose bit is a byte's first: on the bytes already staged
+            const bool mp = bit < hi && s == 0 && (bit >> 3) + 4 <= zbytes && dmx_pf_member_w((uint32_t)L);
+            if (__ballot(mp)) ok = ok || (mp && dmx_pf_member_head(z, zbytes, bit >> 3));
+        }
         const uint64_t am = __ballot(ok);
         if (am) {
             found = b0 + (uint32_t)__builtin_ctzll(am);
@@ -1720,10 +1746,11 @@ __global__ __launch_bounds__(64) void dmx_par_find_kernel(const uint8_t* __restr
     }
 }
 
+template <bool MULTI>
 __global__ __launch_bounds__(64) void dmx_par_measure_kernel(const uint8_t* __restrict__ z, uint64_t zbytes,
-                                                             PPlanHead* __restrict__ h, const uint64_t* __restrict__ cand,
+                                                             PHead<MULTI>* __restrict__ h, const uint64_t* __restrict__ cand,
                                                              dmx_pf_meas* __restrict__ meas, uint32_t nc,
-                                                             uint32_t* __restrict__ gtab) {
+                                                             uint32_t* __restrict__ gtab, uint64_t* __restrict__ mloc) {
     __shared__ InfLDS<IW> S;   // the kernel's one __shared__ object: isym_run addresses the ring from LDS 0
     if (h->st.status) return;
     uint32_t* gt = gtab + (uint64_t)blockIdx.x * ITAB_WORDS;
@@ -1754,11 +1781,44 @@ __global__ __launch_bounds__(64) void dmx_par_measure_kernel(const uint8_t* __re
         o.a = 1;
         o.b = 0;
         ib_init(r, z, zbytes);
-        ib_seek(r, start);
+        if constexpr (!MULTI) ib_seek(r, start);
         uint32_t t = k + 1, skipped = 0, flags = 0, next = 0xFFFFFFFFu;
         int status = 0;
         uint64_t out_len = 0;
+        // a file of members (dmx_pfind.h; the host's measure_multi): nmem members begin in this walk,
+        // the first and the last at the output offsets mfirst and mlast inside it
+        [[maybe_unused]] uint32_t nmem = 0, mfirst = DMX_PF_NOMEM, mlast = DMX_PF_NOMEM;
+        [[maybe_unused]] uint64_t stop = DMX_PF_NONE;   // where the walk ended other than at the reader's position
+        [[maybe_unused]] bool walk = true;
+        if constexpr (MULTI) {
+            uint64_t at = start;
+            if (dmx_pf_at_member(z, start)) {
+                uint64_t body = 0;
+                status = (int)rfl((uint32_t)dmx_gz_head(z + (start >> 3), zbytes - (start >> 3), &body));
+                if (status) {
+                    walk = false;
+                    stop = start;
+                } else {
+                    nmem = 1;
+                    mfirst = mlast = 0;
+                    at = start + 8 * rfl64(body);
+                    const int ld = (int)rfl((uint32_t)dmx_pf_land(cand, nc, &t, at, &skipped));
+                    t = rfl(t);
+                    skipped = rfl(skipped);
+                    if (ld) {
+                        if (ld == 1) next = t;
+                        else flags = DMX_PF_LOST;
+                        walk = false;
+                        stop = at;
+                    }
+                }
+            }
+            ib_seek(r, at);
+        }
         for (;;) {
+            if constexpr (MULTI) {
+                if (!walk) break;
+            }
             bool last = false;
             const int e = ib_status(r, iblock<true, true, IW, false, false>(S, r, o, gt, lane, last));
             status = (int)rfl((uint32_t)e);
@@ -1769,11 +1829,34 @@ __global__ __launch_bounds__(64) void dmx_par_measure_kernel(const uint8_t* __re
                 break;
             }
             if (status) break;
-            if (rfl(last ? 1u : 0u)) {
-                flags = DMX_PF_LAST;
-                break;
+            if constexpr (!MULTI) {
+                if (rfl(last ? 1u : 0u)) {
+                    flags = DMX_PF_LAST;
+                    break;
+                }
             }
-            const uint64_t pos = (uint64_t)rfl(r.wi) * 32 - rfl(r.bc) - 8ull * r.lo;
+            uint64_t pos = (uint64_t)rfl(r.wi) * 32 - rfl(r.bc) - 8ull * r.lo;
+            if constexpr (MULTI) {
+                if (rfl(last ? 1u : 0u)) {
+                    uint64_t q = 0, body = 0;
+                    uint32_t crc = 0, isize = 0;
+                    const int e2 = (int)rfl((uint32_t)dmx_pf_member_end(z, zbytes, pos, &q, &body, &crc, &isize));
+                    q = rfl64(q);
+                    body = rfl64(body);
+                    if (e2 < 0) { status = e2; break; }
+                    if (e2 == 0) { flags = DMX_PF_LAST; break; }
+                    const int l0 = (int)rfl((uint32_t)dmx_pf_land(cand, nc, &t, 8 * q, &skipped));   // at the member's first byte
+                    t = rfl(t);
+                    skipped = rfl(skipped);
+                    if (l0 == 1) { next = t; stop = 8 * q; break; }
+                    if (l0 == 2) { flags = DMX_PF_LOST; break; }
+                    nmem++;
+                    mlast = (uint32_t)out_len;
+                    if (mfirst == DMX_PF_NOMEM) mfirst = mlast;
+                    pos = 8 * (q + body);   // at its first block
+                    ib_seek(r, pos);
+                }
+            }
             const int ld = (int)rfl((uint32_t)dmx_pf_land(cand, nc, &t, pos, &skipped));
             t = rfl(t);
             skipped = rfl(skipped);
@@ -1789,11 +1872,15 @@ __global__ __launch_bounds__(64) void dmx_par_measure_kernel(const uint8_t* __re
         if (lane == 0) {
             dmx_pf_meas m;
             m.end_bit = (uint64_t)rfl(r.wi) * 32 - rfl(r.bc) - 8ull * r.lo;
+            if constexpr (MULTI) {
+                if (stop != DMX_PF_NONE) m.end_bit = stop;
+                mloc[k] = (uint64_t)mfirst | ((uint64_t)mlast << 32);
+            }
             m.out_len = out_len;
             m.next = next;
             m.flags = flags;
             m.status = status;
-            m.reserved = 0;
+            m.reserved = MULTI ? nmem : 0u;
             meas[k] = m;
         }
         __syncthreads();   // the ring and the small arrays are the next candidate's
@@ -1839,11 +1926,21 @@ __global__ void dmx_par_begin_kernel(const PPlanHead* __restrict__ h, uint64_t p
     *d_status = st;
 }
 
+// MULTI (a file of members): the wave crosses the member boundaries inside its chunk -- trailer,
+// header, on at the next body -- and begins at a header when its bit names one.  Output position 0
+// of the decoder is then the member's first byte, not the chunk's: in front of it (o.base = how far
+// the chunk begins behind its member's start, so iblock's own -E_HUFDIS is the member's), and at a
+// member start inside the chunk by flushing and starting over there, so no copy crosses it.  It
+// writes the member records: the begin side of the members whose header it reads, the end side of
+// those whose last block it decodes, at sides[i].mbase + the local count.
+template <bool MULTI>
 __global__ __launch_bounds__(64) void dmx_par_cells_kernel(const uint8_t* __restrict__ z, uint64_t zbytes,
                                                            const dmx_pchunk* __restrict__ chunks, uint8_t* __restrict__ work,
-                                                           PDecCtl* __restrict__ ctl) {
+                                                           PDecCtl* __restrict__ ctl, const uint8_t* __restrict__ plan,
+                                                           dmx_pmember* __restrict__ members, uint32_t max_members) {
     __shared__ InfLDS<IWC, uint16_t> S;   // the kernel's one __shared__ object
     if (!ctl->go) return;
+    [[maybe_unused]] const dmx_pf_mside* sides = MULTI ? pm_sides(plan) : nullptr;
     const uint32_t nlive = ctl->nlive;
     if (blockIdx.x >= dmx_pf_cell_wg(nlive)) return;   // (no table area of its own)
     const uint64_t total = ctl->out_len;
@@ -1877,20 +1974,99 @@ __global__ __launch_bounds__(64) void dmx_par_cells_kernel(const uint8_t* __rest
         o.fl = 0;
         o.a = 1;
         o.b = 0;
+        uint64_t done = 0;   // MULTI: the chunk's output in front of the member the decoder stands in
+        if constexpr (MULTI) {
+            const uint64_t mst = rfl64(sides[i].mstart);
+            if (!err && mst > off) err = -(int)E_RANGE;
+            if (!err) {
+                o.out = (uint8_t*)rfl64((uint64_t)(uintptr_t)(cells + 2 * mst));
+                o.base = off - mst;
+            }
+        }
         if (!err) {
             ib_init(r, z, zbytes);
-            ib_seek(r, bit);
-            for (;;) {   // blocks until exactly end_bit, by the seek-point kernel's rules
+            uint64_t at = bit;
+            bool walk = true;
+            [[maybe_unused]] uint32_t cur = 0;      // members begun in front of the reader
+            [[maybe_unused]] uint64_t mabs = 0;     // where the member the reader stands in began in the output
+            if constexpr (MULTI) {
+                cur = rfl(sides[i].mbase);
+                mabs = rfl64(sides[i].mstart);
+                if (dmx_pf_at_member(z, bit)) {
+                    uint64_t body = 0;
+                    err = (int)rfl((uint32_t)dmx_gz_head(z + (bit >> 3), zbytes - (bit >> 3), &body));
+                    if (!err) {
+                        if (lane == 0 && cur < max_members) {
+                            members[cur].in_off = bit >> 3;
+                            members[cur].out_off = off;
+                        }
+                        cur++;
+                        mabs = off;
+                        o.out = (uint8_t*)rfl64((uint64_t)(uintptr_t)(cells + 2 * off));
+                        o.base = 0;
+                        at = bit + 8 * rfl64(body);
+                        if (at >= end_bit) {   // a header alone
+                            walk = false;
+                            if (at > end_bit) err = -(int)E_SZ;
+                        }
+                    } else {
+                        walk = false;
+                    }
+                }
+            }
+            ib_seek(r, at);
+            while (walk) {   // blocks until exactly end_bit, by the seek-point kernel's rules
                 bool last = false;
                 const int e = ib_status(r, iblock<true, false, IWC, true>(S, r, o, gt, lane, last));
                 err = (int)rfl((uint32_t)e);
                 if (err) break;
                 const uint64_t used = (uint64_t)rfl(r.wi) * 32 - rfl(r.bc) - 8ull * r.lo;
+                if constexpr (MULTI) {
+                    if (rfl(last ? 1u : 0u)) {   // the member's end
+                        io_flush<false>(S, o, o.op, lane);
+                        const uint64_t loc = rfl64(done + o.ob + o.op);   // the chunk's output so far
+                        uint64_t q = 0, body = 0;
+                        uint32_t crc = 0, isize = 0;
+                        const int e2 = (int)rfl((uint32_t)dmx_pf_member_end(z, zbytes, used, &q, &body, &crc, &isize));
+                        q = rfl64(q);
+                        body = rfl64(body);
+                        if (e2 < 0) { err = e2; break; }
+                        if (lane == 0 && cur >= 1 && cur - 1 < max_members) {
+                            members[cur - 1].out_len = off + loc - mabs;
+                            members[cur - 1].crc = crc;
+                            members[cur - 1].isize = isize;
+                        }
+                        if (used == end_bit) {   // the file's end
+                            if (e2 != 0) err = -(int)E_SZ;
+                            break;
+                        }
+                        if (e2 == 0 || 8 * q > end_bit || loc > olen) { err = -(int)E_SZ; break; }
+                        if (8 * q == end_bit) break;   // the next chunk begins at the header
+                        if (lane == 0 && cur < max_members) {
+                            members[cur].in_off = q;
+                            members[cur].out_off = off + loc;
+                        }
+                        cur++;
+                        mabs = off + loc;
+                        done = loc;   // everything is flushed: the decoder starts over at the member's first byte
+                        o.out = (uint8_t*)rfl64((uint64_t)(uintptr_t)(cells + 2 * (off + loc)));
+                        o.base = 0;
+                        o.ob = 0;
+                        o.op = 0;
+                        o.fl = 0;
+                        o.cap = olen - loc;
+                        const uint64_t nb = 8 * (q + body);
+                        if (nb > end_bit) { err = -(int)E_SZ; break; }
+                        ib_seek(r, nb);
+                        if (nb == end_bit) break;
+                        continue;
+                    }
+                }
                 if (used == end_bit) break;
                 if (used > end_bit || rfl(last ? 1u : 0u)) { err = -(int)E_SZ; break; }
             }
         }
-        if (!err && o.ob + o.op != olen) err = -(int)E_SZ;
+        if (!err && done + o.ob + o.op != olen) err = -(int)E_SZ;
         if (!err) io_flush<false>(S, o, o.op, lane);
         if (err && lane == 0) pdec_fail(ctl, i, err);
         __syncthreads();   // the ring and the small arrays are the next chunk's
@@ -1899,18 +2075,29 @@ __global__ __launch_bounds__(64) void dmx_par_cells_kernel(const uint8_t* __rest
 
 #define PTAIL_T 1024u
 #define PTAIL_Q (DMX_PT_WIN / PTAIL_T)   // window positions per thread
+// MULTI: a reference may reach back to its member's first byte only -- the chunk's side says how far
+// that is in front of the chunk, and from which of the chunk's positions on a member began inside it
+// (the cell pass started over there: a reference behind it is before its member whatever it says).
+template <bool MULTI>
 __global__ __launch_bounds__(PTAIL_T) void dmx_par_tails_kernel(const dmx_pchunk* __restrict__ chunks,
-                                                                uint8_t* __restrict__ work, PDecCtl* __restrict__ ctl) {
+                                                                uint8_t* __restrict__ work, PDecCtl* __restrict__ ctl,
+                                                                const uint8_t* __restrict__ plan) {
     // two windows, not one ring: a reference is relative to the chunk's start, so any cell of a long
     // chunk's tail may name any of the 32 768 positions before the chunk
     __shared__ uint8_t win[2][DMX_PT_WIN];
     if (!ctl->go || ctl->err != PDEC_NOERR) return;
+    [[maybe_unused]] const dmx_pf_mside* sides = MULTI ? pm_sides(plan) : nullptr;
     const uint32_t nlive = ctl->nlive, tid = threadIdx.x;
     uint16_t* cells = reinterpret_cast<uint16_t*>(pdec_cells(work, nlive));
     uint32_t cur = 0, bad = 0xFFFFFFFFu;
     for (uint32_t i = 0; i < nlive; i++) {
         const uint64_t off = chunks[i].out_off, len = chunks[i].out_len;
         uint16_t* tc = cells + off + len - dmx_pt_tail(len);   // the tail's cells
+        [[maybe_unused]] uint64_t lim = off, mf = ~0ull;
+        if constexpr (MULTI) {
+            lim = off - sides[i].mstart;
+            if (sides[i].mfirst != DMX_PF_NOMEM) mf = sides[i].mfirst;
+        }
         const uint8_t* W = win[cur];
         uint8_t* N = win[cur ^ 1];
         // window position k = tid + PTAIL_T q of the next window: a tail entry or an old byte
@@ -1925,7 +2112,8 @@ __global__ __launch_bounds__(PTAIL_T) void dmx_par_tails_kernel(const dmx_pchunk
             uint32_t idx;
             int v;
             if (dmx_pt_next(tid + PTAIL_T * q, len, &idx)) {
-                v = dmx_pt_cell(c[q], W, off);
+                if constexpr (MULTI) v = dmx_pt_cell(c[q], W, len - dmx_pt_tail(len) + idx >= mf ? 0 : lim);
+                else v = dmx_pt_cell(c[q], W, off);
                 if (v < 0) {
                     bad = bad < i ? bad : i;
                     v = 0;
@@ -1944,10 +2132,12 @@ __global__ __launch_bounds__(PTAIL_T) void dmx_par_tails_kernel(const dmx_pchunk
 
 #define PPACK_T 256u
 #define PPACK_MAX_WG 4096u
+template <bool MULTI>
 __global__ __launch_bounds__(PPACK_T) void dmx_par_pack_kernel(const dmx_pchunk* __restrict__ chunks,
                                                                uint8_t* __restrict__ work, PDecCtl* __restrict__ ctl,
-                                                               uint8_t* __restrict__ out) {
+                                                               uint8_t* __restrict__ out, const uint8_t* __restrict__ plan) {
     if (!ctl->go || ctl->err != PDEC_NOERR) return;
+    [[maybe_unused]] const dmx_pf_mside* sides = MULTI ? pm_sides(plan) : nullptr;
     const uint32_t nlive = ctl->nlive;
     const uint64_t n = ctl->out_len;   // <= out_cap (begin)
     const uint16_t* cells = reinterpret_cast<const uint16_t*>(pdec_cells(work, nlive));
@@ -1969,7 +2159,13 @@ __global__ __launch_bounds__(PPACK_T) void dmx_par_pack_kernel(const dmx_pchunk*
                 off = chunks[i].out_off;
                 end = off + chunks[i].out_len;
             }
-            int v = dmx_pt_pack(cells, p, off);
+            int v;
+            if constexpr (MULTI) {
+                const uint32_t mf = sides[i].mfirst;
+                v = dmx_pt_pack_lim(cells, p, off, mf != DMX_PF_NOMEM && p - off >= mf ? 0 : off - sides[i].mstart);
+            } else {
+                v = dmx_pt_pack(cells, p, off);
+            }
             if (v < 0) {
                 pdec_fail(ctl, i, -(int)E_HUFDIS);
                 v = 0;
@@ -2107,10 +2303,10 @@ extern "C" int dmx_inflate_parallel_plan_async(const void* d_z, uint64_t zbytes,
     const uint8_t* z = (const uint8_t*)d_z;
     hipLaunchKernelGGL(dmx_par_head_kernel, dim3(1), dim3(1), 0, s, z, zbytes, fmt, chunk, nc, h, cand);
     if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
-    hipLaunchKernelGGL(dmx_par_find_kernel, dim3(nc), dim3(64), 0, s, z, zbytes, h, cand);
+    hipLaunchKernelGGL(dmx_par_find_kernel<false>, dim3(nc), dim3(64), 0, s, z, zbytes, h, cand);
     if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
-    hipLaunchKernelGGL(dmx_par_measure_kernel, dim3((uint32_t)dmx_pf_meas_wg(nc)), dim3(64), 0, s, z, zbytes, h, cand, meas, nc,
-                       gtab);
+    hipLaunchKernelGGL(dmx_par_measure_kernel<false>, dim3((uint32_t)dmx_pf_meas_wg(nc)), dim3(64), 0, s, z, zbytes, h, cand,
+                       meas, nc, gtab, (uint64_t*)nullptr);
     if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
     hipLaunchKernelGGL(dmx_par_link_kernel, dim3(1), dim3(1), 0, s, z, zbytes, h, cand, meas, chunks, nc);
     return hipGetLastError() == hipSuccess ? 0 : -(int)E_DEVICE;
@@ -2134,14 +2330,14 @@ extern "C" int dmx_inflate_parallel_decode_async(const void* d_z, uint64_t zbyte
     hipLaunchKernelGGL(dmx_par_begin_kernel, dim3(1), dim3(1), 0, s, h, plan_bytes, zbytes, max_live, out_cap, work_bytes, ctl,
                        d_status);
     if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
-    hipLaunchKernelGGL(dmx_par_cells_kernel, dim3((uint32_t)dmx_pf_cell_wg(max_live)), dim3(64), 0, s, z, zbytes, chunks, work,
-                       ctl);
+    hipLaunchKernelGGL(dmx_par_cells_kernel<false>, dim3((uint32_t)dmx_pf_cell_wg(max_live)), dim3(64), 0, s, z, zbytes, chunks,
+                       work, ctl, (const uint8_t*)nullptr, (dmx_pmember*)nullptr, 0u);
     if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
-    hipLaunchKernelGGL(dmx_par_tails_kernel, dim3(1), dim3(PTAIL_T), 0, s, chunks, work, ctl);
+    hipLaunchKernelGGL(dmx_par_tails_kernel<false>, dim3(1), dim3(PTAIL_T), 0, s, chunks, work, ctl, (const uint8_t*)nullptr);
     if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
     const uint64_t pw = (out_cap + 4 * PPACK_T - 1) / (4 * PPACK_T);
-    hipLaunchKernelGGL(dmx_par_pack_kernel, dim3(pw < PPACK_MAX_WG ? (pw ? (uint32_t)pw : 1u) : PPACK_MAX_WG), dim3(PPACK_T), 0, s,
-                       chunks, work, ctl, (uint8_t*)d_out);
+    hipLaunchKernelGGL(dmx_par_pack_kernel<false>, dim3(pw < PPACK_MAX_WG ? (pw ? (uint32_t)pw : 1u) : PPACK_MAX_WG),
+                       dim3(PPACK_T), 0, s, chunks, work, ctl, (uint8_t*)d_out, (const uint8_t*)nullptr);
     if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
     if (verify) {
         const uint64_t np = dmx_pf_pieces(out_cap);
@@ -2150,6 +2346,303 @@ extern "C" int dmx_inflate_parallel_decode_async(const void* d_z, uint64_t zbyte
         if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
     }
     hipLaunchKernelGGL(dmx_par_status_kernel, dim3(1), dim3(1), 0, s, work, ctl, verify, d_status);
+    return hipGetLastError() == hipSuccess ? 0 : -(int)E_DEVICE;
+}
+
+// ------------------------------------------------------------------------------------
+// One foreign file of many gzip members (dmx_inflate_parallel_multi_*, include/dmx.h; DESIGN.md 3.1
+// "One foreign file of many members").  The plan and the decode above with MULTI: find also accepts
+// member starts, measure walks over BFINAL, cells crosses the members inside a chunk and writes the
+// member table, tails and pack bound a reference by its member's start.  d_plan = the single plan's
+// parts, then [walks' member offsets 8 x nc][sides 16 x nc], then the tables (dmx_pf_mplan_bytes);
+// d_work = [control][tables][cells] as above, then [segment bases 4 x (nm + 1)][segment CRC-32
+// remainders 4 x (np + nm)] (dmx_pf_mwork).  Its own kernels: head, link, begin, and the segmented
+// check -- segs (one workgroup scans ceil(out_len / 64 KiB) over the members), mcheck (a workgroup
+// per segment: the slice code of dmx_par_check_kernel), mcombine (a thread per member) -- and status.
+// ------------------------------------------------------------------------------------
+__global__ void dmx_parm_head_kernel(const uint8_t* __restrict__ z, uint64_t zbytes, uint32_t chunk, uint32_t nc,
+                                     PMPlanHead* __restrict__ h, uint64_t* __restrict__ cand) {
+    dmx_par_status st;
+    uint64_t body = 0;
+    uint32_t format = 0;
+    st.status = dmx_frame_head(z, zbytes, DMX_BATCH_GZIP, &format, &body);
+    st.format = format;
+    st.out_len = st.in_used = st.work_len = 0;
+    st.check = st.nlive = st.ndead = st.gave_up = 0;
+    st.nchunks = nc;
+    st.ncand = st.status ? 0u : 1u;
+    h->st = st;
+    h->nmembers = 0;
+    h->bad_member = 0xFFFFFFFFu;
+    h->chunk_bytes = chunk;
+    h->isize = 0;
+    h->body_bit = 0;
+    h->zbytes = zbytes;
+    h->next = 0;
+    cand[0] = 0;   // the first header
+}
+
+__global__ void dmx_parm_link_kernel(const uint8_t* __restrict__ z, uint64_t zbytes, PMPlanHead* __restrict__ h,
+                                     const uint64_t* __restrict__ cand, const dmx_pf_meas* __restrict__ meas,
+                                     const uint64_t* __restrict__ mloc, dmx_pchunk* __restrict__ chunks,
+                                     dmx_pf_mside* __restrict__ sides, uint32_t nc) {
+    if (h->st.status) return;
+    dmx_par_multi_status ms;
+    ms.st = h->st;
+    uint32_t isize = 0;
+    dmx_pf_link_multi(z, zbytes, cand, meas, mloc, chunks, sides, nc, &ms, &isize);
+    h->st = ms.st;
+    h->nmembers = ms.nmembers;
+    h->bad_member = ms.bad_member;
+    h->isize = isize;
+}
+
+__device__ __forceinline__ uint32_t* pdec_segbase(uint8_t* work, uint64_t out_len, uint32_t nlive) {
+    return (uint32_t*)(pdec_cells(work, nlive) + dmx_pf_a256(2 * out_len));
+}
+__device__ __forceinline__ uint32_t* pdec_segcrc(uint8_t* work, uint64_t out_len, uint32_t nlive, uint32_t nmembers) {
+    return pdec_segbase(work, out_len, nlive) + dmx_pf_a256(4 * ((uint64_t)nmembers + 1)) / 4;
+}
+
+__global__ void dmx_parm_begin_kernel(const PMPlanHead* __restrict__ h, uint64_t plan_bytes, uint64_t zbytes, uint32_t max_live,
+                                      uint32_t max_members, uint64_t out_cap, uint64_t work_bytes, PDecCtl* __restrict__ ctl,
+                                      dmx_par_multi_status* __restrict__ d_status) {
+    dmx_par_multi_status ms;
+    ms.st = h->st;
+    ms.nmembers = h->nmembers;
+    ms.bad_member = 0xFFFFFFFFu;
+    dmx_par_status& st = ms.st;
+    ctl->next = 0;
+    ctl->err = PDEC_NOERR;
+    ctl->bad = PDEC_NOERR;
+    ctl->go = 0;
+    if (!st.status) {
+        if (h->zbytes != zbytes || !st.nlive || st.nlive > st.nchunks || plan_bytes < dmx_pf_mplan_bytes(st.nchunks) ||
+            st.out_len > DMX_PF_MAX_POS || st.format != DMX_BATCH_GZIP || !ms.nmembers) {
+            st.status = -(int32_t)E_INVAL;
+            st.out_len = st.in_used = st.work_len = 0;
+            st.check = 0;
+            ms.nmembers = 0;
+        } else if (st.nlive > max_live || ms.nmembers > max_members || st.out_len > out_cap ||
+                   work_bytes < dmx_pf_mwork(st.out_len, st.nlive, ms.nmembers)) {
+            st.status = -(int32_t)E_SZ;   // the record holds the needed numbers
+        } else {
+            ctl->out_len = st.out_len;
+            ctl->nlive = st.nlive;
+            ctl->format = st.format;
+            ctl->check = st.check;
+            ctl->isize = h->isize;
+            ctl->nmembers = ms.nmembers;
+            ctl->go = 1;
+        }
+    }
+    *d_status = ms;
+}
+
+// segbase[m] = the segments of the members in front of m, segbase[nm] = all of them: one workgroup,
+// tiles of PSEG_T members, a scan in LDS with the carry in a register.
+#define PSEG_T 1024u
+__global__ __launch_bounds__(PSEG_T) void dmx_parm_segs_kernel(const dmx_pmember* __restrict__ members, uint8_t* __restrict__ work,
+                                                               PDecCtl* __restrict__ ctl) {
+    __shared__ uint32_t sc[PSEG_T];
+    if (!ctl->go || ctl->err != PDEC_NOERR) return;
+    const uint32_t nm = ctl->nmembers, tid = threadIdx.x;
+    uint32_t* segbase = pdec_segbase(work, ctl->out_len, ctl->nlive);
+    uint32_t carry = 0;
+    for (uint32_t m0 = 0; m0 < nm; m0 += PSEG_T) {
+        const uint32_t m = m0 + tid;
+        const uint32_t v = m < nm ? (uint32_t)((members[m].out_len + DMX_PF_PIECE - 1) / DMX_PF_PIECE) : 0u;
+        sc[tid] = v;
+        __syncthreads();
+        for (uint32_t d = 1; d < PSEG_T; d <<= 1) {
+            const uint32_t x = tid >= d ? sc[tid - d] : 0u;
+            __syncthreads();
+            sc[tid] += x;
+            __syncthreads();
+        }
+        if (m < nm) segbase[m] = carry + sc[tid] - v;
+        carry += sc[PSEG_T - 1];
+        __syncthreads();
+    }
+    if (tid == 0) segbase[nm] = carry;
+}
+
+__global__ __launch_bounds__(PCHK_T) void dmx_parm_check_kernel(const uint8_t* __restrict__ out,
+                                                                const dmx_pmember* __restrict__ members,
+                                                                uint8_t* __restrict__ work, PDecCtl* __restrict__ ctl) {
+    __shared__ uint32_t tab[256];
+    __shared__ uint32_t ra[PCHK_T];
+    if (!ctl->go || ctl->err != PDEC_NOERR) return;
+    const uint64_t n = ctl->out_len;
+    const uint32_t nm = ctl->nmembers;
+    const uint32_t* segbase = pdec_segbase(work, n, ctl->nlive);
+    uint32_t* segcrc = pdec_segcrc(work, n, ctl->nlive, nm);
+    const uint32_t nseg = segbase[nm];
+    if (nseg > dmx_pf_pieces(n) + nm) return;   // (a member table that is not the plan's: the combine reports it)
+    const uint32_t tid = threadIdx.x;
+    uint32_t e = tid;
+    for (int k = 0; k < 8; k++) e = (e >> 1) ^ ((0u - (e & 1u)) & DMX_CRC_POLY);
+    tab[tid] = e;
+    const uint32_t xfull = dmx_gf2_xpow((uint64_t)(PCHK_T - 1 - tid) * 256, 3);   // the bytes behind the slice in a full segment
+    __syncthreads();
+    for (uint32_t sg = blockIdx.x; sg < nseg; sg += gridDim.x) {
+        uint32_t lo_m = 0, hi_m = nm;   // the last member whose first segment is at or before sg
+        while (hi_m - lo_m > 1) {
+            const uint32_t mid = lo_m + ((hi_m - lo_m) >> 1);
+            if (segbase[mid] <= sg) lo_m = mid;
+            else hi_m = mid;
+        }
+        const uint64_t mo = members[lo_m].out_off, ml = members[lo_m].out_len;
+        uint64_t lo = mo + (uint64_t)(sg - segbase[lo_m]) * DMX_PF_PIECE, hi = mo + ml;
+        if (mo > n || ml > n - mo || lo > hi) lo = hi = 0;   // never outside out[0, out_len)
+        if (hi - lo > DMX_PF_PIECE) hi = lo + DMX_PF_PIECE;
+        const uint64_t s0 = lo + 256ull * tid < hi ? lo + 256ull * tid : hi, s1 = hi - s0 < 256 ? hi : s0 + 256;
+        uint32_t r = 0, va = 0;
+        for (uint64_t p = s0; p < s1; p++) r = tab[(r ^ out[p]) & 255u] ^ (r >> 8);
+        if (s0 < s1) va = dmx_gf2_mulmod(r, hi - lo == DMX_PF_PIECE ? xfull : dmx_gf2_xpow(hi - s1, 3));
+        ra[tid] = va;
+        __syncthreads();
+        if (tid == 0) {
+            uint32_t x = 0;
+            for (uint32_t k = 0; k < PCHK_T; k++) x ^= ra[k];
+            segcrc[sg] = x;
+        }
+        __syncthreads();
+    }
+}
+
+#define PCMB_T 256u
+#define PCMB_MAX_WG 1024u
+__global__ __launch_bounds__(PCMB_T) void dmx_parm_combine_kernel(const dmx_pmember* __restrict__ members, uint8_t* __restrict__ work,
+                                                                  PDecCtl* __restrict__ ctl) {
+    if (!ctl->go || ctl->err != PDEC_NOERR) return;
+    const uint64_t n = ctl->out_len;
+    const uint32_t nm = ctl->nmembers;
+    const uint32_t* segbase = pdec_segbase(work, n, ctl->nlive);
+    const uint32_t* segcrc = pdec_segcrc(work, n, ctl->nlive, nm);
+    const bool sane = segbase[nm] <= dmx_pf_pieces(n) + nm;
+    const uint32_t xp = dmx_gf2_xpow(DMX_PF_PIECE, 3);
+    for (uint32_t m = blockIdx.x * PCMB_T + threadIdx.x; m < nm; m += gridDim.x * PCMB_T) {
+        const uint64_t len = members[m].out_len;
+        int err = 0;
+        if (!sane) {
+            err = -(int)E_RANGE;
+        } else {
+            uint32_t r = 0;
+            uint64_t left = len;
+            for (uint32_t sg = segbase[m]; sg < segbase[m + 1]; sg++) {   // R(A || B) = R(A) x^(8 |B|) xor R(B)
+                const uint64_t l = left < DMX_PF_PIECE ? left : DMX_PF_PIECE;
+                r = dmx_gf2_mulmod(r, l == DMX_PF_PIECE ? xp : dmx_gf2_xpow(l, 3)) ^ segcrc[sg];
+                left -= l;
+            }
+            // (dmx_crc32_affine's two terms, spelled out: with a second caller in this file the compiler
+            // stops inlining it into dmx_par_status_kernel, which is to stay the code it was)
+            const uint32_t aff = dmx_gf2_mulmod(0xFFFFFFFFu, dmx_gf2_xpow(len, 3)) ^ 0xFFFFFFFFu;
+            if ((r ^ aff) != members[m].crc) err = -(int)E_CRC;
+            else if (members[m].isize != (uint32_t)len) err = -(int)E_LEN;
+        }
+        if (err) atomicMin(&ctl->bad, ((unsigned long long)m << 32) | (uint32_t)err);
+    }
+}
+
+__global__ void dmx_parm_status_kernel(PDecCtl* __restrict__ ctl, dmx_par_multi_status* __restrict__ st) {
+    if (!ctl->go) return;   // the plan's status, -E_INVAL or -E_SZ: begin wrote it
+    int err = ctl->err != PDEC_NOERR ? (int)(uint32_t)(ctl->err & 0xFFFFFFFFull) : 0;
+    if (!err && ctl->bad != PDEC_NOERR) {
+        err = (int)(uint32_t)(ctl->bad & 0xFFFFFFFFull);
+        st->bad_member = (uint32_t)(ctl->bad >> 32);
+    }
+    if (err) {
+        st->st.status = err;
+        st->st.out_len = 0;
+        st->st.in_used = 0;
+        st->st.check = 0;
+        st->st.work_len = 0;
+    }
+}
+
+extern "C" uint64_t dmx_inflate_parallel_multi_plan_work(uint64_t zbytes, uint32_t chunk_bytes) {
+    const uint32_t chunk = par_chunk(chunk_bytes);
+    if (chunk < DMX_PF_MIN_CHUNK || chunk > DMX_PF_MAX_CHUNK || zbytes > DMX_PF_MAX_POS) return 0;
+    return dmx_pf_mplan_bytes(dmx_pf_nchunks(zbytes, chunk));
+}
+
+extern "C" int dmx_inflate_parallel_multi_plan_async(const void* d_z, uint64_t zbytes, uint32_t fmt, uint32_t chunk_bytes,
+                                                     void* d_plan, uint64_t plan_bytes, void* stream) {
+    if (!d_plan || (!d_z && zbytes) || ((uintptr_t)d_plan & 255)) return -(int)E_INVAL;
+    if (fmt != DMX_BATCH_AUTO && fmt != DMX_BATCH_GZIP) return -(int)E_INVAL;
+    const uint32_t chunk = par_chunk(chunk_bytes);
+    if (chunk < DMX_PF_MIN_CHUNK || chunk > DMX_PF_MAX_CHUNK) return -(int)E_INVAL;
+    if (zbytes > DMX_PF_MAX_POS) return -(int)E_RANGE;
+    const uint32_t nc = dmx_pf_nchunks(zbytes, chunk);
+    if (plan_bytes < dmx_pf_mplan_bytes(nc)) return -(int)E_INVAL;
+    hipStream_t s = (hipStream_t)stream;
+    uint8_t* P = (uint8_t*)d_plan;
+    PMPlanHead* h = (PMPlanHead*)P;
+    dmx_pchunk* chunks = (dmx_pchunk*)(P + 256);
+    uint64_t* cand = (uint64_t*)(P + 256 + dmx_pf_a256(32ull * nc));
+    dmx_pf_meas* meas = (dmx_pf_meas*)((uint8_t*)cand + dmx_pf_a256(8ull * nc));
+    uint64_t* mloc = (uint64_t*)((uint8_t*)meas + dmx_pf_a256(32ull * nc));
+    dmx_pf_mside* sides = (dmx_pf_mside*)((uint8_t*)mloc + dmx_pf_a256(8ull * nc));
+    uint32_t* gtab = (uint32_t*)((uint8_t*)sides + dmx_pf_a256(16ull * nc));
+    const uint8_t* z = (const uint8_t*)d_z;
+    hipLaunchKernelGGL(dmx_parm_head_kernel, dim3(1), dim3(1), 0, s, z, zbytes, chunk, nc, h, cand);
+    if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
+    hipLaunchKernelGGL(dmx_par_find_kernel<true>, dim3(nc), dim3(64), 0, s, z, zbytes, h, cand);
+    if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
+    hipLaunchKernelGGL(dmx_par_measure_kernel<true>, dim3((uint32_t)dmx_pf_meas_wg(nc)), dim3(64), 0, s, z, zbytes, h, cand, meas,
+                       nc, gtab, mloc);
+    if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
+    hipLaunchKernelGGL(dmx_parm_link_kernel, dim3(1), dim3(1), 0, s, z, zbytes, h, cand, meas, mloc, chunks, sides, nc);
+    return hipGetLastError() == hipSuccess ? 0 : -(int)E_DEVICE;
+}
+
+extern "C" uint64_t dmx_inflate_parallel_multi_work(uint64_t out_cap, uint32_t max_live, uint32_t max_members) {
+    return dmx_pf_mwork(out_cap, max_live, max_members);
+}
+
+extern "C" int dmx_inflate_parallel_multi_decode_async(const void* d_z, uint64_t zbytes, const void* d_plan, uint64_t plan_bytes,
+                                                       uint32_t max_live, uint32_t max_members, void* d_out, uint64_t out_cap,
+                                                       dmx_pmember* d_members, void* d_work, uint64_t work_bytes, int verify,
+                                                       dmx_par_multi_status* d_status, void* stream) {
+    if (!d_plan || !d_work || !d_status || (!d_z && zbytes) || (!d_out && out_cap) || (!d_members && max_members))
+        return -(int)E_INVAL;
+    if (((uintptr_t)d_plan & 255) || ((uintptr_t)d_work & 255) || ((uintptr_t)d_status & 7) || ((uintptr_t)d_members & 7))
+        return -(int)E_INVAL;
+    if (plan_bytes < dmx_pf_mplan_bytes(1) || work_bytes < 256) return -(int)E_INVAL;
+    if (zbytes > DMX_PF_MAX_POS) return -(int)E_RANGE;
+    hipStream_t s = (hipStream_t)stream;
+    const PMPlanHead* h = (const PMPlanHead*)d_plan;
+    const dmx_pchunk* chunks = (const dmx_pchunk*)((const uint8_t*)d_plan + 256);
+    uint8_t* work = (uint8_t*)d_work;
+    PDecCtl* ctl = (PDecCtl*)work;
+    const uint8_t* z = (const uint8_t*)d_z;
+    hipLaunchKernelGGL(dmx_parm_begin_kernel, dim3(1), dim3(1), 0, s, h, plan_bytes, zbytes, max_live, max_members, out_cap,
+                       work_bytes, ctl, d_status);
+    if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
+    const uint8_t* plan = (const uint8_t*)d_plan;
+    hipLaunchKernelGGL(dmx_par_cells_kernel<true>, dim3((uint32_t)dmx_pf_cell_wg(max_live)), dim3(64), 0, s, z, zbytes, chunks,
+                       work, ctl, plan, d_members, max_members);
+    if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
+    hipLaunchKernelGGL(dmx_par_tails_kernel<true>, dim3(1), dim3(PTAIL_T), 0, s, chunks, work, ctl, plan);
+    if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
+    const uint64_t pw = (out_cap + 4 * PPACK_T - 1) / (4 * PPACK_T);
+    hipLaunchKernelGGL(dmx_par_pack_kernel<true>, dim3(pw < PPACK_MAX_WG ? (pw ? (uint32_t)pw : 1u) : PPACK_MAX_WG),
+                       dim3(PPACK_T), 0, s, chunks, work, ctl, (uint8_t*)d_out, plan);
+    if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
+    if (verify) {
+        hipLaunchKernelGGL(dmx_parm_segs_kernel, dim3(1), dim3(PSEG_T), 0, s, (const dmx_pmember*)d_members, work, ctl);
+        if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
+        const uint64_t ns = dmx_pf_pieces(out_cap) + max_members;
+        hipLaunchKernelGGL(dmx_parm_check_kernel, dim3(ns < PCHK_MAX_WG ? (uint32_t)ns : PCHK_MAX_WG), dim3(PCHK_T), 0, s,
+                           (const uint8_t*)d_out, (const dmx_pmember*)d_members, work, ctl);
+        if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
+        const uint32_t cw = (max_members + PCMB_T - 1) / PCMB_T;
+        hipLaunchKernelGGL(dmx_parm_combine_kernel, dim3(cw < PCMB_MAX_WG ? (cw ? cw : 1u) : PCMB_MAX_WG), dim3(PCMB_T), 0, s,
+                           (const dmx_pmember*)d_members, work, ctl);
+        if (hipGetLastError() != hipSuccess) return -(int)E_DEVICE;
+    }
+    hipLaunchKernelGGL(dmx_parm_status_kernel, dim3(1), dim3(1), 0, s, ctl, d_status);
     return hipGetLastError() == hipSuccess ? 0 : -(int)E_DEVICE;
 }
 

@@ -219,6 +219,90 @@ dmx_pf_meas measure(const uint8_t* z, uint64_t n, const uint64_t* cand, uint32_t
     return m;
 }
 
+// What a multi-member walk tells the host plan about the members it meets (the device's cell pass
+// writes the same table): begin and end events in file order, offsets inside the walk.
+struct MemberSink {
+    dmx_pmember* m;
+    uint32_t cap, n;    // n: members begun so far
+    uint64_t off;       // the output offset of the walk's chunk
+    void begin(uint64_t in_off, uint64_t local) {
+        if (n < cap) {
+            m[n].in_off = in_off;
+            m[n].out_off = off + local;
+            m[n].out_len = 0;
+            m[n].crc = m[n].isize = 0;
+        }
+        n++;
+    }
+    void end(uint64_t local, uint32_t crc, uint32_t isize) {   // of the member begun last
+        if (n == 0 || n > cap) return;
+        m[n - 1].out_len = off + local - m[n - 1].out_off;
+        m[n - 1].crc = crc;
+        m[n - 1].isize = isize;
+    }
+};
+
+// the measure pass of chunk k of a file of members: over BFINAL, the trailer and the next header,
+// standing at the member's first byte and at its first block (dmx_pfind.h)
+dmx_pf_meas measure_multi(const uint8_t* z, uint64_t n, const uint64_t* cand, uint32_t nc, uint32_t k, uint64_t* mloc,
+                          MemberSink& sink) {
+    const uint64_t max_out = DMX_PF_MAX_CHUNK_OUT;
+    HB s = {z, n, cand[k]};
+    dmx_pf_meas m;
+    memset(&m, 0, sizeof(m));
+    m.next = 0xFFFFFFFFu;
+    uint32_t t = k + 1, skipped = 0, first = DMX_PF_NOMEM, lastm = DMX_PF_NOMEM;
+    bool open = false;   // a landing is due before the next block
+    if (dmx_pf_at_member(z, s.pos)) {
+        uint64_t body = 0;
+        m.status = dmx_gz_head(z + (s.pos >> 3), n - (s.pos >> 3), &body);
+        if (!m.status) {
+            sink.begin(s.pos >> 3, 0);
+            m.reserved = 1;
+            first = lastm = 0;
+            s.pos += 8 * body;
+            open = true;
+        }
+    }
+    while (!m.status) {
+        if (open) {
+            const int ld = dmx_pf_land(cand, nc, &t, s.pos, &skipped);
+            if (ld == 1) { m.next = t; break; }
+            if (ld == 2) { m.flags = DMX_PF_LOST; break; }
+            open = false;
+        }
+        bool last = false;
+        m.status = hb_status(s, hb_block(s, &m.out_len, &last, max_out + 1));
+        if (m.status == -(int)E_SZ || (!m.status && m.out_len > max_out)) {   // too much for one chunk
+            m.status = 0;
+            m.flags = DMX_PF_LOST;
+            break;
+        }
+        if (m.status) break;
+        open = true;
+        if (!last) continue;
+        uint64_t q, body;
+        uint32_t crc, isize;
+        const int r = dmx_pf_member_end(z, n, s.pos, &q, &body, &crc, &isize);
+        if (r < 0) { m.status = r; break; }
+        sink.end(m.out_len, crc, isize);
+        if (r == 0) { m.flags = DMX_PF_LAST; break; }
+        const uint64_t e = s.pos;
+        s.pos = 8 * q;   // at the member's first byte
+        const int ld = dmx_pf_land(cand, nc, &t, s.pos, &skipped);
+        if (ld == 1) { m.next = t; break; }
+        if (ld == 2) { s.pos = e; m.flags = DMX_PF_LOST; break; }
+        sink.begin(q, m.out_len);
+        m.reserved++;
+        lastm = (uint32_t)m.out_len;
+        if (first == DMX_PF_NOMEM) first = lastm;
+        s.pos = 8 * (q + body);   // at its first block
+    }
+    m.end_bit = s.pos;
+    mloc[k] = (uint64_t)first | ((uint64_t)lastm << 32);
+    return m;
+}
+
 }   // namespace
 
 // The serial walk over the blocks of z[0, n) from `bit` (internal; tests/c/pfind_model.cpp counts
@@ -290,6 +374,64 @@ extern "C" int dmx_inflate_parallel_plan_host(const void* zv, uint64_t zbytes, u
     free(cand);
     free(meas);
     return st->nlive > cap ? -(int)E_SZ : 0;
+}
+
+// ---- one file of many gzip members (include/dmx.h: dmx_inflate_parallel_multi_plan_host) ----------
+extern "C" int dmx_inflate_parallel_multi_plan_host(const void* zv, uint64_t zbytes, uint32_t fmt, uint32_t chunk_bytes,
+                                                    dmx_pchunk* chunks, uint32_t cap, dmx_pmember* members, uint32_t mcap,
+                                                    dmx_par_multi_status* ms) {
+    if (!ms || (!zv && zbytes) || (!chunks && cap) || (!members && mcap)) return -(int)E_INVAL;
+    if (fmt != DMX_BATCH_AUTO && fmt != DMX_BATCH_GZIP) return -(int)E_INVAL;
+    const uint32_t chunk = chunk_bytes ? chunk_bytes : DMX_PF_DEF_CHUNK;
+    if (chunk < DMX_PF_MIN_CHUNK || chunk > DMX_PF_MAX_CHUNK) return -(int)E_INVAL;
+    if (zbytes > DMX_PF_MAX_POS) return -(int)E_RANGE;
+    const uint8_t* z = (const uint8_t*)zv;
+    const uint32_t nc = dmx_pf_nchunks(zbytes, chunk);
+    memset(ms, 0, sizeof(*ms));
+    ms->bad_member = 0xFFFFFFFFu;
+    dmx_par_status* st = &ms->st;
+    st->nchunks = nc;
+    uint64_t body = 0;
+    st->status = dmx_frame_head(z, zbytes, DMX_BATCH_GZIP, &st->format, &body);
+    if (st->status) return 0;
+    uint64_t* cand = (uint64_t*)malloc(8ull * nc);
+    uint64_t* mloc = (uint64_t*)malloc(8ull * nc);
+    dmx_pf_meas* meas = (dmx_pf_meas*)calloc(nc, sizeof(dmx_pf_meas));
+    dmx_pf_mside* sides = (dmx_pf_mside*)malloc(sizeof(dmx_pf_mside) * (cap ? cap : 1ull));
+    if (!cand || !mloc || !meas || !sides) {
+        free(cand);
+        free(mloc);
+        free(meas);
+        free(sides);
+        return -(int)E_MALLOC;
+    }
+    cand[0] = 0;   // the first header
+    st->ncand = 1;
+    for (uint32_t c = 1; c < nc; c++) {
+        uint64_t lo, hi;
+        dmx_pf_range(c, chunk, zbytes, 0, &lo, &hi);
+        cand[c] = DMX_PF_NONE;
+        for (uint64_t bit = lo; bit < hi; bit++)
+            if (((bit & 7) == 0 && dmx_pf_member(z, zbytes, bit >> 3)) || dmx_pf_valid(z, zbytes, bit)) {
+                cand[c] = bit;
+                st->ncand++;
+                break;
+            }
+    }
+    MemberSink sink = {members, mcap, 0, 0};
+    for (uint32_t i = 0;;) {
+        meas[i] = measure_multi(z, zbytes, cand, nc, i, mloc, sink);
+        sink.off += meas[i].out_len;
+        if (meas[i].status || meas[i].flags) break;
+        i = meas[i].next;
+    }
+    uint32_t isize = 0;
+    dmx_pf_link_multi(z, zbytes, cand, meas, mloc, chunks, sides, cap, ms, &isize);
+    free(cand);
+    free(mloc);
+    free(meas);
+    free(sides);
+    return st->nlive > cap || ms->nmembers > mcap ? -(int)E_SZ : 0;
 }
 
 // ---- seek points from a plan's live chunks (include/dmx.h: dmx_zindex_from_chunks_host) ----------

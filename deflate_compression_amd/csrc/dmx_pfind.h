@@ -13,6 +13,7 @@
 #include <string.h>
 
 #include "../../include/dmx.h"
+#include "dmx_gz_head.h"
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define DMX_PF_HD __host__ __device__
@@ -298,6 +299,126 @@ static inline DMX_PF_HD void dmx_pf_link(const uint8_t* z, uint64_t zbytes, cons
     st->out_len = status ? 0 : off;
     if (status) { st->in_used = 0; st->check = 0; }
     st->work_len = status ? 0 : dmx_pf_work(off, nlive);
+}
+
+// ---- one file of many gzip members (dmx_inflate_parallel_multi_*, include/dmx.h; DESIGN.md 3.1
+// "One foreign file of many members").  The text above serves it unchanged; what follows is the
+// second kind of candidate, the step over a member's end, and the link that also scans the members.
+#define DMX_PF_NOMEM 0xFFFFFFFFu   // a walk without a member start
+
+// what the link leaves per live chunk besides its dmx_pchunk (16 bytes)
+struct dmx_pf_mside {
+    uint64_t mstart;   // the output offset at which the member the chunk begins in began
+    uint32_t mbase;    // members that begin in front of the chunk: the index of the first that begins in it
+    uint32_t mfirst;   // the output offset inside the chunk of its first member start, or DMX_PF_NOMEM
+};
+
+// d_plan: the single plan's parts, then [walks' member offsets 8 x nc][sides 16 x nc], then the tables
+static inline DMX_PF_HD uint64_t dmx_pf_mplan_bytes(uint32_t nc) {
+    return dmx_pf_plan_bytes(nc) + dmx_pf_a256(8ull * nc) + dmx_pf_a256(16ull * nc);
+}
+// d_work: [control 256][tables][cells 2 x out_len] as dmx_pf_work, then [segment bases 4 x (nm + 1)]
+// [segment CRC-32 remainders 4 x (np + nm)]: a member of n bytes has ceil(n / DMX_PF_PIECE) segments
+static inline DMX_PF_HD uint64_t dmx_pf_mwork(uint64_t out_len, uint32_t nlive, uint32_t nmembers) {
+    return 256 + 8192 * dmx_pf_cell_wg(nlive) + dmx_pf_a256(2 * out_len) + dmx_pf_a256(4 * ((uint64_t)nmembers + 1)) +
+           dmx_pf_a256(4 * (dmx_pf_pieces(out_len) + nmembers));
+}
+
+// A member may start at byte p: 1F 8B 08, no reserved flag bit (dmx_pf_member_w: on the four bytes
+// the caller holds), a whole header, and a first block that is not of type 3.
+static inline DMX_PF_HD bool dmx_pf_member_w(uint32_t w) { return (w & 0xE0FFFFFFu) == 0x00088B1Fu; }
+static inline DMX_PF_HD bool dmx_pf_member_head(const uint8_t* z, uint64_t n, uint64_t p) {
+    uint64_t body = 0;
+    if (dmx_gz_head(z + p, n - p, &body) != 0) return false;
+    return ((dmx_pf_peek(z, n, 8 * (p + body)) >> 1) & 3) != 3;
+}
+static inline DMX_PF_HD bool dmx_pf_member(const uint8_t* z, uint64_t n, uint64_t p) {
+    return p + 4 <= n && dmx_pf_member_w((uint32_t)dmx_pf_load64(z, n, p)) && dmx_pf_member_head(z, n, p);
+}
+// the candidate at `bit` is a member start, not a block: 1F reads as BFINAL 1 / BTYPE 3, which the
+// block filter refuses, so the two kinds never meet at one position.  Chunk 0's is bit 0, the first header.
+static inline DMX_PF_HD bool dmx_pf_at_member(const uint8_t* z, uint64_t bit) { return (bit & 7) == 0 && z[bit >> 3] == 0x1F; }
+
+// A measure walk's final block ended at bit e: the trailer and the rule behind it.  Returns 0 where
+// the file ends (trailing data included), 1 where a member follows at byte *q with its data at
+// *q + *body, or a status: -E_CRC for a trailer cut short, the next header's error.  *q is the
+// byte behind the trailer, *crc and *isize what it stores.
+static inline DMX_PF_HD int dmx_pf_member_end(const uint8_t* z, uint64_t zbytes, uint64_t e, uint64_t* q, uint64_t* body,
+                                              uint32_t* crc, uint32_t* isize) {
+    const uint64_t p = (e + 7) >> 3;
+    *q = p;
+    *body = 0;
+    *crc = *isize = 0;
+    if (p + 8 > zbytes) return -(int)E_CRC;
+    uint32_t c = 0, sz = 0;
+    for (uint32_t k = 0; k < 4; k++) c |= (uint32_t)z[p + k] << (8 * k);
+    for (uint32_t k = 0; k < 4; k++) sz |= (uint32_t)z[p + 4 + k] << (8 * k);
+    *crc = c;
+    *isize = sz;
+    *q = p + 8;
+    if (p + 10 > zbytes || z[p + 8] != 0x1F || z[p + 9] != 0x8B) return 0;
+    const int r = dmx_gz_head(z + p + 8, zbytes - (p + 8), body);
+    return r ? r : 1;
+}
+
+// dmx_pf_link for a file of members: mloc[i] holds walk i's first (low half) and last (high half)
+// member start as output offsets inside the walk, DMX_PF_NOMEM for none; meas[i].reserved the
+// members that begin in it.  Writes the sides next to the chunks.  st->st.format is gzip.
+static inline DMX_PF_HD void dmx_pf_link_multi(const uint8_t* z, uint64_t zbytes, const uint64_t* cand, const dmx_pf_meas* meas,
+                                               const uint64_t* mloc, dmx_pchunk* chunks, dmx_pf_mside* sides, uint32_t cap,
+                                               dmx_par_multi_status* ms, uint32_t* isize) {
+    (void)zbytes;   // (a walk with DMX_PF_LAST has seen its whole trailer)
+    dmx_par_status* st = &ms->st;
+    uint32_t i = 0, nlive = 0, nmem = 0;
+    uint64_t off = 0, mstart = 0;
+    int32_t status = 0;
+    st->gave_up = 0;
+    st->in_used = 0;
+    st->check = 0;
+    *isize = 0;
+    for (;;) {
+        const dmx_pf_meas m = meas[i];
+        const uint32_t first = (uint32_t)mloc[i], last = (uint32_t)(mloc[i] >> 32);
+        if (nlive < cap) {
+            chunks[nlive].bit = cand[i];
+            chunks[nlive].end_bit = m.end_bit;
+            chunks[nlive].out_off = off;
+            chunks[nlive].out_len = m.out_len;
+            sides[nlive].mstart = mstart;
+            sides[nlive].mbase = nmem;
+            sides[nlive].mfirst = first;
+        }
+        nlive++;
+        if (last != DMX_PF_NOMEM) mstart = off + last;
+        nmem += m.reserved;
+        off += m.out_len;
+        if (m.status) { status = m.status; break; }
+        if ((m.flags & DMX_PF_LOST) || m.out_len > DMX_PF_MAX_CHUNK_OUT) {
+            st->gave_up = 1;
+            status = -(int32_t)E_RANGE;
+            break;
+        }
+        if (off > DMX_PF_MAX_POS) { status = -(int32_t)E_RANGE; break; }
+        if (m.flags & DMX_PF_LAST) {
+            const uint64_t p = (m.end_bit + 7) >> 3;
+            uint32_t c = 0, sz = 0;
+            for (uint32_t k = 0; k < 4; k++) c |= (uint32_t)z[p + k] << (8 * k);
+            for (uint32_t k = 0; k < 4; k++) sz |= (uint32_t)z[p + 4 + k] << (8 * k);
+            st->check = c;
+            st->in_used = p + 8;
+            *isize = sz;
+            break;
+        }
+        i = m.next;
+    }
+    st->status = status;
+    st->nlive = nlive;
+    st->ndead = st->ncand - nlive;
+    st->out_len = status ? 0 : off;
+    if (status) { st->in_used = 0; st->check = 0; }
+    st->work_len = status ? 0 : dmx_pf_mwork(off, nlive, nmem);
+    ms->nmembers = status ? 0 : nmem;
+    ms->bad_member = 0xFFFFFFFFu;
 }
 
 #endif

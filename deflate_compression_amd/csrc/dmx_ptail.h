@@ -70,4 +70,16 @@ static inline DMX_PT_HD int dmx_pt_pack(const uint16_t* cells, uint64_t p, uint6
     return s < DMX_PT_REF ? (int)s : -1;
 }
 
+// dmx_pt_pack for a file of members (dmx_inflate_parallel_multi_decode_async): a reference may reach
+// `limit` bytes in front of the chunk at most -- to its member's first byte; 0 behind a member start
+// inside the chunk.  (dmx_pt_cell takes the same limit in place of out_off.)
+static inline DMX_PT_HD int dmx_pt_pack_lim(const uint16_t* cells, uint64_t p, uint64_t chunk_off, uint64_t limit) {
+    const uint32_t c = cells[p];
+    if (c < DMX_PT_REF) return (int)c;
+    const uint32_t b = dmx_pt_back(c);
+    if (b > limit || b > chunk_off) return -1;
+    const uint32_t s = cells[chunk_off - b];
+    return s < DMX_PT_REF ? (int)s : -1;
+}
+
 #endif

@@ -778,6 +778,73 @@ int dmx_inflate_parallel_decode_async(const void* d_z, uint64_t zbytes, const vo
                                       uint32_t max_live, void* d_out, uint64_t out_cap,
                                       void* d_work, uint64_t work_bytes, int verify,
                                       dmx_par_status* d_status, void* stream);
+/* One foreign file of many gzip members, in one pass (csrc/dmx_pfind.h, csrc/dmx_inflate_par_host.cpp,
+ * csrc/dmx_inflate_dev.hip; DESIGN.md §3.1 "One foreign file of many members"): what `cat a.gz b.gz`,
+ * `gzip -c >> log.gz`, pgzip, Hadoop and WARC writers leave.  The calls above stop at the first
+ * trailer; these go on.  gzip only: fmt is DMX_BATCH_AUTO or DMX_BATCH_GZIP (ZLIB and RAW: -E_INVAL),
+ * and a file that does not begin 1F 8B has status -E_ZHEAD under both.
+ *   The rule behind a member's 8-byte trailer, at byte q: the file ends there; or z[q], z[q + 1] are
+ *   1F 8B and a member follows, whose header is read as the first one's (its error is the file's
+ *   status: -E_ZCMPMT, -E_RESERV, -E_ZHEAD for a header cut short); anything else -- zero padding,
+ *   junk, a lone 1F as the last byte -- is trailing data and ignored, in_used = q.  A trailer cut
+ *   short is -E_CRC.  The output is the members' data back to back; a match distance that reaches
+ *   before its own member's first byte is -E_HUFDIS.
+ *   The plan is the single stream's with a second kind of candidate, a member start: a byte p inside
+ *   the chunk with 1F 8B 08, no reserved flag bit, a header that dmx_gz_head accepts and a first
+ *   block that is not of type 3.  A chunk's candidate is the lowest bit offset either rule accepts.
+ *   A measure walk does not stop at BFINAL: it takes the trailer, applies the rule above, and stands
+ *   at the member's first byte (bit 8 q) and at its first block (behind the header), so a candidate
+ *   of either kind ends it.  Chunk 0 begins at bit 0, the first header.  end_bit of a live chunk is
+ *   bit of the next (a chunk that ends with a member ends at bit 8 q of the next; the last one at the
+ *   end of the last block), out_off the exclusive scan of out_len; a chunk may be a header alone, with
+ *   out_len 0.
+ * dmx_pmember (32 bytes) names a member: in_off the byte of its 1F, out_off / out_len its data in the
+ * output, crc and isize as its trailer stores them.  dmx_par_multi_status (64 bytes) is a
+ * dmx_par_status (check: the last member's stored CRC-32; ncand counts both kinds; work_len for
+ * dmx_inflate_parallel_multi_work(out_len, nlive, nmembers)) with nmembers and bad_member: the first
+ * member in file order whose CRC-32 or ISIZE is wrong where the status is -E_CRC / -E_LEN from the
+ * check, else 0xFFFFFFFF.
+ * dmx_inflate_parallel_multi_plan_host: the plan on the host.  chunks receives at most cap live
+ * chunks, members at most mcap member records (the model for the device's table); -E_SZ where
+ * nlive > cap or nmembers > mcap, with both counts in the record.  Otherwise as
+ * dmx_inflate_parallel_plan_host (-E_INVAL also for members NULL with mcap > 0 and fmt ZLIB / RAW).
+ * dmx_inflate_parallel_multi_plan_async: four launches as dmx_inflate_parallel_plan_async; d_plan
+ * (256-byte aligned, plan_bytes >= dmx_inflate_parallel_multi_plan_work(zbytes, chunk_bytes)) holds
+ * the dmx_par_multi_status at offset 0, the live chunks at 256, and behind the single plan's parts
+ * (before the tables) the walks' member offsets (8 nc) and 16 bytes per live chunk: the output
+ * offset at which the member it begins in began, the index of the first member that begins in it,
+ * and the output offset inside it of its first member start.  Record and chunks equal the host
+ * plan's field for field.
+ * dmx_inflate_parallel_multi_decode_async: begin, cells, tails, pack, with verify != 0 the segmented
+ * check (segment scan, CRC-32 remainders per segment of at most 64 KiB that never crosses a member,
+ * a combine per member), status.  A wave per live chunk crosses the member boundaries inside its
+ * chunk (trailer, header, on at the next body) and writes d_members: the begin side (in_off,
+ * out_off) of the members whose header it reads, the end side (out_len, crc, isize) of those whose
+ * last block it decodes.  *d_status (8-byte aligned, 64 bytes) as dmx_inflate_parallel_decode_async's,
+ * with -E_SZ also for nmembers > max_members (the record holds the needed nlive, nmembers, out_len
+ * and work_len) and, with verify != 0, per member the CRC-32 and then ISIZE mod 2^32: -E_CRC, -E_LEN,
+ * bad_member the first such member.  With verify == 0 neither is looked at.  No byte at or beyond
+ * out_cap and no record at or beyond max_members is ever written.  The rules of the single calls hold:
+ * no allocation, no host synchronisation, grids from the host arguments alone (zbytes, chunk_bytes,
+ * max_live, max_members, out_cap, verify), every record and counter reset by a kernel of the call,
+ * surplus workgroups leave at once, after a status no later stage runs.  d_members: 8-byte aligned,
+ * max_members records.  dmx_inflate_parallel_multi_work(out_cap, max_live, max_members) bytes of
+ * d_work always suffice (a multiple of 256, monotone in all three).  Argument errors return before
+ * any device call, as for the single calls (also d_members NULL with max_members > 0 or not 8-byte
+ * aligned, fmt ZLIB / RAW).  An index of seek points across members is not built. */
+typedef struct { uint64_t in_off, out_off, out_len; uint32_t crc, isize; } dmx_pmember;      /* 32 bytes */
+typedef struct { dmx_par_status st; uint32_t nmembers, bad_member; } dmx_par_multi_status;   /* 64 bytes */
+int dmx_inflate_parallel_multi_plan_host(const void* z, uint64_t zbytes, uint32_t fmt, uint32_t chunk_bytes,
+                                         dmx_pchunk* chunks, uint32_t cap, dmx_pmember* members, uint32_t mcap,
+                                         dmx_par_multi_status* st);
+uint64_t dmx_inflate_parallel_multi_plan_work(uint64_t zbytes, uint32_t chunk_bytes);
+int dmx_inflate_parallel_multi_plan_async(const void* d_z, uint64_t zbytes, uint32_t fmt, uint32_t chunk_bytes,
+                                          void* d_plan, uint64_t plan_bytes, void* stream);
+uint64_t dmx_inflate_parallel_multi_work(uint64_t out_cap, uint32_t max_live, uint32_t max_members);
+int dmx_inflate_parallel_multi_decode_async(const void* d_z, uint64_t zbytes, const void* d_plan, uint64_t plan_bytes,
+                                            uint32_t max_live, uint32_t max_members, void* d_out, uint64_t out_cap,
+                                            dmx_pmember* d_members, void* d_work, uint64_t work_bytes, int verify,
+                                            dmx_par_multi_status* d_status, void* stream);
 /* One foreign stream, indexed once and read many times: seek points (csrc/dmx_inflate.c,
  * csrc/dmx_inflate_dev.hip; DESIGN.md §3.1 "Seek points").  The index of zran, indexed_gzip and
  * rapidgzip's --export-index: the stream is decoded once, serially and exactly, on the host, and at
