@@ -26,6 +26,8 @@ include/dmx.h).  This module is a thin ctypes layer:
     zindex_build(z) -> ZIndex                             ONE such stream indexed once on the host: seek points with windows
     inflate_parallel_indexed(zt) -> (out, ZIndex)         ... decoded in one pass on the device, which leaves the same index there
     inflate_indexed(zt, ix) / zindex_pread(zt, ix, off, n)  ... then decoded a wave per point, or only the points a range touches
+    zip_index(z) / zip_index_gpu(zt) -> ZipIndex          a ZIP archive's entries, found on the host / where it lies on the device
+    zip_read(zt, index, which) / unzip(z)                 ... any selection of them decoded in one chain of launches, CRC-32 checked
     compress_batch(bufs)                                  many independent buffers into as many streams, in one chain of launches
     Encoder                                               device-resident encodes
 
@@ -56,6 +58,8 @@ __all__ = [
     "ZIndex", "ZIndexStatus", "zindex_build", "inflate_points_async", "inflate_indexed", "zindex_read_ranges", "zindex_pread",
     "DMX_ZINDEX_WINDOW", "DMX_ZINDEX_DEF_SPAN", "DMX_ZINDEX_MAX_SPAN",
     "zindex_from_parallel_async", "inflate_parallel_indexed",
+    "ZipEntryDTYPE", "ZipStatus", "ZipIndex", "zip_index", "zip_index_gpu", "zip_index_async", "zip_read_async", "zip_read",
+    "unzip", "DMX_ZIP_VERIFY",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -81,6 +85,7 @@ DMX_RANGES_VIRTUAL = 1
 DMX_BATCH_AUTO, DMX_BATCH_ZLIB, DMX_BATCH_GZIP, DMX_BATCH_RAW = 0, 1, 2, 3
 DMX_BATCH_MEASURE = 16
 DMX_BATCH_NODICT = 0xFFFFFFFF
+DMX_ZIP_VERIFY = 1
 DMX_ZINDEX_WINDOW = 32768
 DMX_ZINDEX_DEF_SPAN = 256 << 10
 DMX_ZINDEX_MAX_SPAN = 1 << 30
@@ -190,6 +195,18 @@ class ZIndexStatus(ctypes.Structure):
                 ("span", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+class ZipStatus(ctypes.Structure):
+    """dmx_zip_status: the 40-byte record of dmx_zip_index_host / dmx_zip_index_async"""
+    _fields_ = [("status", ctypes.c_int32), ("nentries", ctypes.c_uint32), ("out_len", ctypes.c_uint64),
+                ("cd_off", ctypes.c_uint64), ("cd_len", ctypes.c_uint64), ("ncand", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+# numpy's view of dmx_zip_entry records (64 bytes)
+ZipEntryDTYPE = [("data_off", "<u8"), ("csize", "<u8"), ("usize", "<u8"), ("out_off", "<u8"), ("hdr_off", "<u8"),
+                 ("name_off", "<u8"), ("crc", "<u4"), ("status", "<i4"), ("method", "<u2"), ("flags", "<u2"),
+                 ("name_len", "<u2"), ("reserved", "<u2")]
+
 # numpy's view of dmx_pchunk records
 PCHUNK_DTYPE = [("bit", "<u8"), ("end_bit", "<u8"), ("out_off", "<u8"), ("out_len", "<u8")]
 
@@ -282,6 +299,13 @@ def lib() -> ctypes.CDLL:
         "dmx_inflate_batch_dict_work": ([u32, u32], u64),
         "dmx_inflate_batch_dict_async": ([vp, u64, vp, u32, u32, vp, u64, vp, u32, vp, vp, u64, vp, vp, u64, vp, vp],
                                          ctypes.c_int),
+        "dmx_zip_index_host": ([vp, u64, vp, u32, ctypes.POINTER(ZipStatus)], ctypes.c_int),
+        "dmx_zip_index_work": ([u64, u32], u64),
+        "dmx_zip_index_async": ([vp, u64, vp, u32, vp, u64, vp, vp], ctypes.c_int),
+        "dmx_zip_read_work": ([u32], u64),
+        "dmx_zip_read_async": ([vp, u64, vp, u32, vp, u32, u32, vp, u64, vp, vp, vp, u64, vp, vp], ctypes.c_int),
+        "dmx_zip_index_geometry": ([u32p], None),
+        "dmx_zip_read_geometry": ([u32p], None),
         "dmx_inflate_dict_host": ([vp, u64, u32, vp, u64, ctypes.POINTER(vp), ctypes.POINTER(u64), ctypes.POINTER(u64)],
                                   ctypes.c_int),
         "dmx_inflate_parallel_plan_host": ([vp, u64, u32, u32, vp, u32, ctypes.POINTER(ParStatus)], ctypes.c_int),
@@ -956,6 +980,217 @@ def inflate_batch(z, streams=None, fmt: str = "auto", sizes=None, strict: bool =
     if strict and rec.nfailed:
         raise DeflateError(int(results["status"][rec.first_bad]), f"inflate_batch: stream {rec.first_bad}")
     return out[:total], offsets, results
+
+
+# ---- ZIP archives (include/dmx.h: dmx_zip_index_host, dmx_zip_index_async, dmx_zip_read_async) ----
+
+class ZipIndex:
+    """The entries of a ZIP archive: `entries` a uint8 CUDA tensor of 64-byte dmx_zip_entry records
+    (None for an index made on the host until zip_read uploads it), `host` the same records as a
+    numpy structured array (ZipEntryDTYPE), `status` the ZipStatus record.  len() is the number of
+    entries held; names are fetched lazily -- only the central directory's bytes go to the host --
+    and decoded as zipfile decodes them: UTF-8 where flag bit 11 is set, else cp437."""
+
+    def __init__(self, host, status: ZipStatus, entries=None, source=None):
+        self.host = host
+        self.status = status
+        self.entries = entries
+        self._source = source   # the archive: bytes-like or a CUDA tensor
+        self._names = None
+        self._by_name = None
+
+    def __len__(self) -> int:
+        return int(self.host.shape[0])
+
+    @property
+    def out_len(self) -> int:
+        return int(self.status.out_len)
+
+    @property
+    def names(self) -> list:
+        if self._names is None:
+            a, n = int(self.status.cd_off), int(self.status.cd_len)
+            src = self._source
+            if hasattr(src, "is_cuda"):
+                cd = src[a:a + n].cpu().numpy().tobytes()
+            else:
+                cd = bytes(memoryview(src)[a:a + n])
+            out = []
+            for e in self.host:
+                o = int(e["name_off"]) - a
+                raw = cd[o:o + int(e["name_len"])]
+                out.append(raw.decode("utf-8") if int(e["flags"]) & 0x800 else raw.decode("cp437"))
+            self._names = out
+        return self._names
+
+    def find(self, name: str) -> int:
+        """the index of the last entry with this name (zipfile's rule for duplicates); KeyError if none"""
+        if self._by_name is None:
+            self._by_name = {nm: i for i, nm in enumerate(self.names)}
+        return self._by_name[name]
+
+    def device_entries(self, dev):
+        import torch
+        if self.entries is None or self.entries.device != dev:
+            import numpy as np
+            raw = np.ascontiguousarray(self.host).view(np.uint8).reshape(-1)
+            self.entries = torch.from_numpy(raw.copy() if raw.size else np.zeros(64, np.uint8)).to(dev)[:raw.size]
+        return self.entries
+
+
+def zip_index(z, cap: int | None = None) -> ZipIndex:
+    """The index of a ZIP archive in host memory (dmx_zip_index_host: no GPU).  Raises DeflateError with
+    the file's status (-E_SZ only where cap is given and too small); an entry's own status is in its
+    record and fails nothing here."""
+    import numpy as np
+    L = lib()
+    p, n, keep = _buf(z)
+    st = ZipStatus()
+    if cap is None:
+        _check(L.dmx_zip_index_host(p, n, None, 0, ctypes.byref(st)), "dmx_zip_index_host")
+        if st.status not in (0, -E["E_SZ"]):
+            raise DeflateError(st.status, "dmx_zip_index_host")
+        cap = st.nentries
+    ent = np.zeros(max(cap, 1), dtype=ZipEntryDTYPE)
+    _check(L.dmx_zip_index_host(p, n, ctypes.c_void_p(ent.ctypes.data), cap, ctypes.byref(st)), "dmx_zip_index_host")
+    del keep
+    if st.status:
+        raise DeflateError(st.status, "dmx_zip_index_host")
+    return ZipIndex(ent[:st.nentries], st, source=z)
+
+
+def zip_index_async(zt, entries, cap: int, work, status, stream=None) -> int:
+    """dmx_zip_index_async on caller-owned CUDA tensors, enqueued on `stream` (the current one by
+    default) with no synchronisation, so it can be captured into a graph: zt the archive (uint8, any
+    alignment), entries a uint8 tensor of 64 x cap bytes, work a uint8 tensor of
+    lib().dmx_zip_index_work(zt.numel(), max_cand) bytes (256-byte aligned), status a 40-byte uint8
+    tensor (ZipStatus).  Returns the call's own return code; the outcome is in the record."""
+    import torch
+    dev = work.device
+    with torch.cuda.device(dev):
+        s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        return lib().dmx_zip_index_async(_ptr(zt), zt.numel(), _ptr(entries), cap, ctypes.c_void_p(work.data_ptr()),
+                                         work.numel(), ctypes.c_void_p(status.data_ptr()), ctypes.c_void_p(s))
+
+
+def zip_read_async(zt, entries, nentries: int, sel, nsel: int, flags: int, out, out_bytes: int, offsets, results, work,
+                   status, stream=None) -> int:
+    """dmx_zip_read_async on caller-owned CUDA tensors, as zip_index_async (no synchronisation: it can
+    be captured into a graph): entries / nentries as an index call wrote them, sel an int32 / uint32
+    tensor of nsel selectors or None (all entries, nsel == nentries), flags 0 or DMX_ZIP_VERIFY,
+    offsets an int64 tensor of nsel + 1, results a tensor of 32 x nsel bytes (BResult records), work
+    a uint8 tensor of lib().dmx_zip_read_work(nsel) bytes, status a 16-byte tensor (BatchStatus)."""
+    import torch
+    dev = work.device
+    with torch.cuda.device(dev):
+        s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        return lib().dmx_zip_read_async(_ptr(zt), zt.numel(), _ptr(entries), nentries, _ptr(sel), nsel, flags, _ptr(out),
+                                        out_bytes, ctypes.c_void_p(offsets.data_ptr()), ctypes.c_void_p(results.data_ptr()),
+                                        ctypes.c_void_p(work.data_ptr()), work.numel(), ctypes.c_void_p(status.data_ptr()),
+                                        ctypes.c_void_p(s))
+
+
+def zip_index_gpu(zt, cap: int | None = None, stream=None, _max_cand: int | None = None) -> ZipIndex:
+    """The index of a ZIP archive that lies in device memory, made on the device (dmx_zip_index_async):
+    zt is a contiguous uint8 CUDA tensor, any alignment.  The same record and entries as zip_index
+    gives for the same bytes.  cap: room for that many entries (-E_SZ where the archive has more);
+    by default zt.numel() // 46, which no archive exceeds.  The work buffer holds cap + 1024
+    candidates; an archive whose names, extras and comments spell more headers than that is
+    indexed once more with the number the first pass reports.  Synchronises the stream to read the
+    40-byte record and the entries' host view."""
+    import numpy as np
+    import torch
+    L = lib()
+    dev = zt.device
+    n = zt.numel()
+    if n and (zt.dtype != torch.uint8 or not zt.is_cuda or not zt.is_contiguous()):
+        raise ValueError("zip_index_gpu takes a contiguous uint8 CUDA tensor")
+    room = n // 46 if cap is None else cap
+    max_cand = room + 1024 if _max_cand is None else _max_cand   # (_max_cand: the tests' way into the second pass)
+    with torch.cuda.device(dev):
+        s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        for attempt in (0, 1):
+            work = torch.empty(int(L.dmx_zip_index_work(n, max_cand)), dtype=torch.uint8, device=dev)
+            entries = torch.empty(max(room, 1) * 64, dtype=torch.uint8, device=dev)
+            st = torch.empty(40, dtype=torch.uint8, device=dev)
+            _check(zip_index_async(zt, entries, room, work, st, s), "dmx_zip_index_async")
+            if stream is not None:
+                torch.cuda.synchronize(dev)
+            rec = ZipStatus.from_buffer_copy(st.cpu().numpy().tobytes())
+            if rec.status == -E["E_SZ"] and rec.nentries == 0 and rec.ncand > max_cand and attempt == 0:
+                max_cand = rec.ncand
+                continue
+            break
+    if rec.status:
+        raise DeflateError(rec.status, "dmx_zip_index_async")
+    entries = entries[:rec.nentries * 64]
+    host = entries.cpu().numpy().view(ZipEntryDTYPE) if rec.nentries else np.zeros(0, dtype=ZipEntryDTYPE)
+    return ZipIndex(host, rec, entries=entries, source=zt)
+
+
+def zip_read(zt, index: ZipIndex | None = None, which=None, verify: bool = True, strict: bool = True):
+    """Decode entries of a ZIP archive that lies in device memory (dmx_zip_read_async): zt a contiguous
+    uint8 CUDA tensor, index what zip_index_gpu / zip_index gave for it (made here by default), which
+    a list of names or entry numbers in any order, repeats allowed (None: all, in archive order).
+    Returns (out, offsets, results): the decoded bytes packed back to back in selection order as a
+    uint8 CUDA tensor, an int64 CUDA tensor of n + 1 with selection k at out[offsets[k]:offsets[k + 1]],
+    and a numpy structured array of the BResult records (status, format = the method, out_len,
+    in_used, check = the stored CRC-32).  verify: every entry's CRC-32 is checked on the device
+    (-E_CRC).  The output's size comes from the index's host view, so the read itself makes no
+    synchronisation before its results are fetched.  strict: an entry with a status raises
+    DeflateError with the status of the lowest such selection, which the message names."""
+    import numpy as np
+    import torch
+    L = lib()
+    if zt.numel() and (zt.dtype != torch.uint8 or not zt.is_cuda or not zt.is_contiguous()):
+        raise ValueError("zip_read takes a contiguous uint8 CUDA tensor")
+    dev = zt.device
+    if index is None:
+        index = zip_index_gpu(zt)
+    ne = len(index)
+    if which is None:
+        sel_h, sel = np.arange(ne, dtype=np.int64), None
+    else:
+        sel_h = np.array([index.find(w) if isinstance(w, str) else int(w) for w in which], dtype=np.int64)
+        sel = torch.from_numpy(sel_h.astype(np.uint32).view(np.int32).copy()).to(dev) if sel_h.size else None
+    n = int(sel_h.size)
+    ok = (sel_h >= 0) & (sel_h < ne)
+    lens = np.zeros(n, dtype=np.uint64)
+    if ne:
+        picked = index.host[np.where(ok, sel_h, 0)]
+        lens = np.where(ok & (picked["status"] == 0), picked["usize"], 0).astype(np.uint64)
+    total = int(lens.sum())
+    with torch.cuda.device(dev):
+        entries = index.device_entries(dev)
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        res = torch.zeros(max(n, 1) * 4, dtype=torch.int64, device=dev)
+        st = torch.empty(2, dtype=torch.int64, device=dev)
+        work = torch.empty(int(L.dmx_zip_read_work(n)), dtype=torch.uint8, device=dev)
+        if which is not None and n == 0:
+            sel = torch.zeros(1, dtype=torch.int32, device=dev)   # (an empty selection is not "all")
+        _check(zip_read_async(zt, entries, ne, sel, n, DMX_ZIP_VERIFY if verify else 0, out if total else None, total,
+                              offsets, res, work, st), "dmx_zip_read_async")
+        results = res.view(max(n, 1), 4)[:n].cpu().numpy().view(np.uint8).reshape(-1).view(BRESULT_DTYPE)
+        rec = BatchStatus.from_buffer_copy(st.cpu().numpy().tobytes())
+    if strict and rec.nfailed:
+        raise DeflateError(int(results["status"][rec.first_bad]), f"zip_read: selection {rec.first_bad}")
+    return out[:total], offsets, results
+
+
+def unzip(z) -> dict:
+    """{name: bytes} of a ZIP archive in host memory, decoded on the GPU: the archive is uploaded,
+    indexed on the device (zip_index_gpu), every entry decoded and its CRC-32 checked there
+    (zip_read), and the bytes brought back.  Raises DeflateError for an archive that does not index
+    or an entry that does not decode."""
+    import torch
+    zb = bytes(z)
+    zt = torch.frombuffer(bytearray(zb or b"\0"), dtype=torch.uint8).cuda()[:len(zb)]
+    index = zip_index_gpu(zt)
+    out, offsets, _ = zip_read(zt, index)
+    data = out.cpu().numpy().tobytes()
+    off = offsets.cpu().numpy()
+    return {nm: data[int(off[k]):int(off[k + 1])] for k, nm in enumerate(index.names)}
 
 
 def _par_info(rec: ParStatus) -> dict:

@@ -1559,6 +1559,9 @@ extern "C" int dmx_inflate_batch_dict_async(const void* d_z, uint64_t zbytes, co
     return dmx_crc32_batch_launch(d_out, out_bytes, d_streams, nstreams, d_results, d_status, s);
 }
 
+// The entries of a ZIP archive: the batch decode on its raw path, a copy kernel for stored entries
+#include "dmx_zip_read.inc"
+
 // Seek points: d_work as the batch decode's -- [IBatchCtl, 256 B][first-level tables].  The grid is
 // the batch kernel's too: the same InfLDS<IW> is the limit per CU.
 extern "C" uint64_t dmx_inflate_points_work(uint32_t nsel) { return dmx_inflate_batch_work(nsel); }

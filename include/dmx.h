@@ -1192,6 +1192,94 @@ uint32_t dmx_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
 /* The CRC kernel's geometry (tests): bytes per workgroup span and per lane slice. */
 void dmx_crc32_geometry(uint32_t* span, uint32_t* lane_slice);
 
+/* ZIP archives (csrc/dmx_zip.h, dmx_zip_host.cpp, dmx_zip_dev.hip, dmx_zip_read.inc):
+ * the container around raw DEFLATE streams and stored bytes that .npz, .jar, .whl, .docx and most
+ * "dataset in one file" bundles use.  An index of the archive's entries, made on the host or -- for
+ * an archive that lies in device memory -- on the device, and a batched decode of any selection of
+ * entries with every entry's length and CRC-32 checked on the device.
+ * The end record is found by the rule of CPython's zipfile: the last 22 bytes where they begin
+ * PK\5\6 and end in a zero comment length, else the last PK\5\6 whose first byte lies within the final
+ * 65 557 bytes; a ZIP64 locator (PK\6\7) 20 bytes in front of it and the ZIP64 end record (PK\6\6) 56
+ * bytes in front of that replace its fields.  concat = end record - cd_size - cd_off (less 76 with
+ * the ZIP64 records) is added to every stored offset, so prefixed and self-extracting archives work.
+ * Entry fields come from the central directory (sizes and CRC-32 always, so data descriptors need no
+ * handling), the ZIP64 extra (id 0x0001: usize, csize, header offset, each only where the 32-bit
+ * value is 0xFFFFFFFF) and the local header, whose own name and extra lengths place the data.
+ * The record: status 0 or
+ *   -E_ZHEAD  no end record (or one cut short), or ZIP64 markers with a locator but no ZIP64 record
+ *   -E_RANGE  zbytes > 0xFFFFFFF0 (the decoder's bound), disk numbers other than 0 / 0 / equal
+ *             counts (or the locator's), more than 2^32 - 1 entries, the directory outside the file
+ *   -E_LEN    the chain of headers from cd_off is not exactly nentries headers ending at cd_off + cd_len
+ *   -E_SZ     cap < nentries: the first cap entries are written, nentries and out_len are the full values
+ * (device only: -E_SZ with nentries 0 and ncand set where the work buffer holds too few candidates).
+ * After -E_ZHEAD, -E_RANGE, -E_LEN no entry is written and nentries / out_len are 0; cd_off / cd_len
+ * are set once the end record parsed.  ncand is 0 but in that one device status, where it is the
+ * number of positions of the directory that parse as headers: the candidates a work buffer must hold.
+ * An entry: where its data lies (data_off, csize), its decoded length, out_off = the exclusive sum of
+ * usize over the entries with status 0 before it (archive order), hdr_off = the local header (concat
+ * added), name_off / name_len = the name's bytes inside the central directory, crc, method, flags and
+ * a status of its own, which never fails the file: -E_ZCMPMT (method other than 0 and 8), -E_RESERV
+ * (flag bit 0 or 6: encrypted), -E_ZHEAD (local header's signature wrong, or the header cut),
+ * -E_RANGE (data_off + csize outside the file), -E_LEN (stored with csize != usize) -- the first of
+ * these in this order.  Entries with a status count 0 bytes in out_off and out_len. */
+typedef struct { int32_t status; uint32_t nentries; uint64_t out_len; uint64_t cd_off; uint64_t cd_len;
+                 uint32_t ncand; uint32_t reserved; } dmx_zip_status;            /* 40 bytes */
+typedef struct { uint64_t data_off, csize, usize, out_off; uint64_t hdr_off, name_off; uint32_t crc; int32_t status;
+                 uint16_t method, flags, name_len, reserved; } dmx_zip_entry;    /* 64 bytes */
+/* Host only, no GPU: the serial walk.  Returns 0 (the outcome is in *status) or -E_INVAL (status
+ * NULL, z NULL with zbytes > 0, entries NULL with cap > 0). */
+int dmx_zip_index_host(const void* z, uint64_t zbytes, dmx_zip_entry* entries, uint32_t cap, dmx_zip_status* status);
+/* The same record and entries for the same bytes in device memory, with dmx_bgzf_index_async's
+ * contract: no context, no allocation, no host synchronisation; the number of launches and every
+ * grid follow from zbytes, cap and work_bytes alone, a linear chain that can be captured into a graph;
+ * the record is reset by a kernel of the call.  d_z may have any alignment; whole aligned 16-byte
+ * groups are loaded: up to 15 bytes before the first and after the last byte of the directory, inside
+ * the groups that hold them, are read and never looked at.  Everything lives in d_work (256-byte
+ * aligned, work_bytes >= dmx_zip_index_work(zbytes, max_cand), a multiple of 256, monotone in both);
+ * the candidates it holds follow from work_bytes.
+ * Returns before any device call: -E_INVAL (d_status or d_work NULL, d_z NULL with zbytes > 0,
+ * d_entries NULL with cap > 0; d_entries or d_status not 8-byte, d_work not 256-byte aligned;
+ * work_bytes < dmx_zip_index_work(zbytes, 1)), -E_RANGE (zbytes > 0xFFFFFFF0); else 0 or -E_DEVICE. */
+uint64_t dmx_zip_index_work(uint64_t zbytes, uint32_t max_cand);
+int dmx_zip_index_async(const void* d_z, uint64_t zbytes, dmx_zip_entry* d_entries, uint32_t cap,
+                        void* d_work, uint64_t work_bytes, dmx_zip_status* d_status, void* stream);
+/* The decode of a selection of entries.  d_entries / nentries are what an index call wrote for d_z.
+ * d_sel == NULL: all entries in archive order (nsel must equal nentries); else nsel selectors in any
+ * order, repeats allowed.  The selected entries land packed back to back in selection order:
+ * d_offsets (nsel + 1 words, 8-byte aligned) is the exclusive sum of len_k = the entry's usize, or 0
+ * where the index gave it a status or the selector is >= nentries; a prepare kernel computes it.
+ * Deflated entries go through dmx_inflate_batch_async's decode on its raw path (a wave per entry: one
+ * very large deflated entry runs at the one-stream rate), stored entries through a copy kernel, a
+ * workgroup per 64 KiB span of output.  flags: DMX_ZIP_VERIFY checks every entry's CRC-32.
+ * d_results[k] as dmx_inflate_batch_async writes it, with format = the method and check = the stored
+ * CRC-32; status: the entry's index status; the decoder's own; -E_SZ when more than usize bytes
+ * come out, -E_LEN when fewer do or the stream needs bytes past csize; -E_CRC; -E_RANGE for a selector
+ * >= nentries, or an entry whose data lies outside d_z[0, zbytes) or whose usize is above 2^43 (more
+ * than DEFLATE makes of 0xFFFFFFF0 bytes; len_k is then 0 too).  d_status as there.  A failing
+ * entry never changes a neighbour's bytes or result; no byte outside [0, d_offsets[nsel]) is written.
+ * out_bytes smaller than d_offsets[nsel]: the call cannot know without a synchronisation and returns
+ * 0; the prepare kernel sees it, nothing is decoded or written, every d_results[k].status is -E_SZ,
+ * nfailed == nsel, first_bad == 0 and total_out holds the bytes needed (d_offsets is complete), so a
+ * captured graph reports it on every replay.
+ * Six or seven launches (reset, prepare, decode, copy, fix-up, the CRC-32 pass under DMX_ZIP_VERIFY,
+ * finalise), reset and prepare alone when nsel == 0: no allocation, no host synchronisation, a linear chain
+ * whose grids follow from nsel, out_bytes and the device's size.  d_work: 256-byte aligned,
+ * work_bytes >= dmx_zip_read_work(nsel) (a multiple of 256, monotone).
+ * Returns before any device call: -E_INVAL (d_results, d_status, d_work or d_offsets NULL, d_entries
+ * NULL with nentries > 0, d_z NULL with zbytes > 0, d_out NULL with out_bytes > 0, d_sel NULL with
+ * nsel != nentries; d_entries, d_offsets, d_results or d_status not 8-byte, d_sel not 4-byte, d_work
+ * not 256-byte aligned; work_bytes too small), -E_RANGE (unknown flags, zbytes > 0xFFFFFFF0); else 0
+ * or -E_DEVICE. */
+#define DMX_ZIP_VERIFY 1u
+uint64_t dmx_zip_read_work(uint32_t nsel);
+int dmx_zip_read_async(const void* d_z, uint64_t zbytes, const dmx_zip_entry* d_entries, uint32_t nentries,
+                       const uint32_t* d_sel, uint32_t nsel, uint32_t flags, void* d_out, uint64_t out_bytes,
+                       uint64_t* d_offsets, dmx_bresult* d_results, void* d_work, uint64_t work_bytes,
+                       dmx_batch_status* d_status, void* stream);
+/* The geometry (tests): bytes per scan tile of the index, bytes per span of the copy kernel. */
+void dmx_zip_index_geometry(uint32_t* tile);
+void dmx_zip_read_geometry(uint32_t* span);
+
 /* Seeded synthetic inputs for the bench/tests (host, deterministic). */
 void dmx_gen_text(uint8_t* buf, uint64_t n, uint64_t seed);    /* enwik-style wiki text */
 void dmx_gen_random(uint8_t* buf, uint64_t n, uint64_t seed);  /* splitmix64 bytes */
