@@ -35,6 +35,7 @@
 #include "dmx_internal.h"
 #include "dmx_extbits.h"
 #include "dmx_walk.h"
+#include "dmx_sort_slices.h"
 #include "../../include/dmx.h"
 
 #define MAXLEN 258
@@ -1444,12 +1445,14 @@ __device__ __forceinline__ uint32_t deep_samples(uint32_t nvalid) {
 
 // Bucket-sorted positions S (stable by position inside a bucket) by ONE counting pass over
 // the 13-bit bucket (round 5; the two-pass LSD sort below stays as the checked fallback).
-// The block's positions form four groups of 8192 (g = w >> 2 for wave w; round 6: two groups
-// of 16384 until round 5); T[h] (in len8) holds the counts of bucket h of groups
+// The block's positions form 16 slices of 2048 in four groups of 8192 (dmx_sort_slices.h:
+// slice s = 4g + r of group g ranks in round r and is run by wave 4g + ((g + r) & 3), so that
+// a round's four waves sit on four SIMDs -- the hardware places the waves of equal w & 3 on
+// one; round 6: two groups of 16384 until round 5); T[h] (in len8) holds the counts of bucket h of groups
 // 0 and 1 in its low and high 16 bits, T2[h] (in S's first half, free until the scatter)
 // those of groups 2 and 3.
-//  1. every wave hashes its 2048 positions [2048w, 2048w + 2048) into registers;
-//  2. four rounds, one wave of each group per round (wave w in round w & 3), separated by
+//  1. every wave hashes its slice's 2048 positions [2048s, 2048s + 2048) into registers;
+//  2. four rounds, one slice of each group per round (slice s in round s & 3), separated by
 //     barriers: the wave adds 1 << 16 (g & 1) to its group's word of bucket h for its 32
 //     steps of 64 positions and keeps the old field as the entry's rank.  Inside a round a
 //     wave's LDS instructions execute in order and same-address lanes of one instruction in
@@ -1466,7 +1469,7 @@ __device__ __forceinline__ uint32_t deep_samples(uint32_t nvalid) {
 // DEEP with deep_dk > 0 (the trigram sort of a DMX_F_DEEP launch whose two depths are both
 // at most KD, match_block): the block's chain depth by block_chain's rule, from this sort's
 // own hashes.  Block_chain's samples, p mod 2048 < 256, are steps 0..3 of every wave
-// (x = 2048 w + lane + 64 st), so their buckets are hh[0] and hh[1]: they go into the
+// (x = 2048 s + lane + 64 st), so their buckets are hh[0] and hh[1]: they go into the
 // 8192-bit set in L.hist (zero until P3) before the first ranking round, four waves that do
 // not rank in the second round count the set, zero it again and add into L.ntok (zero until
 // the search), and the sum is read after the rounds.  Returns the depth (else max_chain).
@@ -1474,7 +1477,8 @@ template <bool RUNCHK, int NB, bool DEEP>
 __device__ __forceinline__ int32_t count_sort_positions(MatchLDS& L, uint32_t bn, int32_t max_chain, uint32_t tid,
                                                         bool stamp, uint64_t* tp0, int32_t deep_dk) {
     static_assert(!DEEP || NB == 3, "the depth statistic hashes trigrams");
-    const uint32_t lane = tid & 63, wave = wave_of(tid);
+    // the wave's slice, not its index, is what means a position range, a group and a round below
+    const uint32_t lane = tid & 63, slice = dmx_sort_slice_of_wave(wave_of(tid));
     const uint32_t nvalid = bn > 2 ? bn - 2 : 0;   // positions with a full trigram
     const bool need_starts = max_chain <= 0 || max_chain > KD;
     uint32_t* T = reinterpret_cast<uint32_t*>(L.len8);   // 8192 counter pairs (len8 is free in P0)
@@ -1487,11 +1491,11 @@ __device__ __forceinline__ int32_t count_sort_positions(MatchLDS& L, uint32_t bn
     reinterpret_cast<uint4*>(T2)[tid] = z4;
     reinterpret_cast<uint4*>(T2)[tid + MT] = z4;
     constexpr uint32_t NR = 4;
-    uint32_t* Tg = (wave >> 3) ? T2 : T;
-    const uint32_t sh = ((wave >> 2) & 1) << 4;   // this wave's group field
+    uint32_t* Tg = (dmx_sort_slice_group(slice) >> 1) ? T2 : T;
+    const uint32_t sh = (dmx_sort_slice_group(slice) & 1) << 4;   // this slice's group field
     __syncthreads();   // (also: the staged block, for callers without a barrier after staging)
     const uint64_t lt = (1ull << lane) - 1ull;
-    uint32_t x0l = (wave << 11) + lane, nvl = nvalid;
+    uint32_t x0l = (slice << 11) + lane, nvl = nvalid;
     uint32_t hh[16];   // bucket of each of this lane's 32 entries, two per register
     asm volatile("" : "+v"(x0l), "+v"(nvl));
 #pragma unroll
@@ -1515,15 +1519,15 @@ __device__ __forceinline__ int32_t count_sort_positions(MatchLDS& L, uint32_t bn
 #pragma unroll
     for (int j = 0; j < 16; j++) rk[j] = 0;
     for (uint32_t r = 0; r < NR; r++) {
-        // the set is complete after the first round's barrier: waves 0, 2, 4 and 6 (which rank
-        // in rounds 0 and 2) count 64 of its 256 words each
-        if (deep && r == 1 && wave < 8 && !(wave & 1)) {
-            const uint32_t k = (wave << 5) + lane;
+        // the set is complete after the first round's barrier: the waves of slices 0, 2, 4 and
+        // 6 (which rank in rounds 0 and 2) count 64 of its 256 words each
+        if (deep && r == 1 && slice < 8 && !(slice & 1)) {
+            const uint32_t k = (slice << 5) + lane;
             const uint32_t c = wave_sum_u32((uint32_t)__popc(L.hist[k]));
             L.hist[k] = 0;
             if (lane == 0) atomicAdd(&L.ntok, c);
         }
-        if (r == (wave & (NR - 1))) {
+        if (r == dmx_sort_slice_round(slice)) {
             asm volatile("" : "+v"(x0l), "+v"(nvl));
             if (RUNCHK) {
 #pragma unroll
